@@ -6,13 +6,20 @@ N GPUs = tensor parallel (the reference's docs/tensor_parallelism.md split): QKV
 (column-parallel), O / down split K by whole quantization groups (row-parallel) followed by a sum all-reduce through
 the library's C-ABI parallel context (nad_pc_*: RCCL over xGMI on the caller's stream).
 
-The same JSON line also carries the other BASELINE configs as secondary workloads (never the headline `value`):
-Llama-2-7B int4-g128 with GPTQ-style zero points (config 3) and Mistral-7B int2-g64 with the reference's int2 quant
-policy (config 5: wv and w2 stay int4, llama_utils.cpp:269-287), each with its own algorithmic bytes and roofline.
+A plain run does only what the headline needs: it builds the stack, warms up, times K graph-replayed decode steps and
+prints the result line (`value` = tokens/s, `ms_per_step` = milliseconds per timed step).
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+--full adds everything else to the same JSON line: the eager decode path, the 2048-token prefill, the per-launch
+roofline, the synthetic K = N = 4096 sweep, the CPU baseline, and the other BASELINE configs as secondary workloads
+(never the headline `value`): Llama-2-7B int4-g128 with GPTQ-style zero points (config 3) and Mistral-7B int2-g64 with
+the reference's int2 quant policy (config 5: wv and w2 stay int4, llama_utils.cpp:269-287), each with its own
+algorithmic bytes and roofline.
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
   --gpus N > 1 without a torch.distributed environment re-launches this script as N ranks under
   torch.distributed.run (a child process, started before anything touches the GPU) and exits with its status.
+  --dump-outputs DIR writes what the last timed decode step computed as DIR/<name>.npy (float32); weights and inputs
+  are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -174,6 +181,28 @@ class Runner:
             if self.world > 1:
                 self.pc.reduce_add(self.ffn)
         st.lm_head.forward(self.x, out=self.logits)
+
+    def outputs(self):
+        """What a caller of step() receives (the last layer's Q/K/V, O and FFN outputs, and the logits)."""
+        if self.st.cfg["fuse_qkv"]:
+            qkv = {"qkv": self.qkv}
+        else:
+            qkv = {"q": self.qkv[0], "k": self.kv[0], "v": self.kv[1]}
+        return dict(qkv, o=self.o, ffn=self.ffn, logits=self.logits)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(runner, directory, rank, world):
+    """Write runner.outputs() as directory/<name>.npy in float32 (tensor-parallel ranks: <name>_rank<r>.npy)."""
+    arrays = {name: t.detach().float().cpu().numpy() for name, t in runner.outputs().items()}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, total
+    os.makedirs(directory, exist_ok=True)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, f"{name}{suffix}.npy"), a)
 
 
 def graph_time(fn, reps, torch):
@@ -453,11 +482,16 @@ def main(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--prefill-steps", type=int, default=10)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the eager decode path, prefill, the per-launch roofline, the synthetic sweep, "
+                         "the secondary BASELINE workloads and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the outputs of the last timed decode step as DIR/<name>.npy (float32)")
+    ap.add_argument("--prefill-steps", type=int, default=10, help="with --full")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the secondary BASELINE workloads")
-    ap.add_argument("--no-synthetic", action="store_true", help="skip the synthetic K=N=4096 M sweep")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the secondary BASELINE workloads")
+    ap.add_argument("--no-synthetic", action="store_true", help="with --full: skip the synthetic K=N=4096 M sweep")
     ap.add_argument("--dry-run", action="store_true", help="print the rank layout and exit (no GPU)")
     args = ap.parse_args(argv)
 
@@ -520,7 +554,7 @@ def main(argv=None):
             dt = pc.max_over_ranks(dt)
         return dt
 
-    # ---- decode (headline): M = 1, one launch per WOQ matmul (graph-replayed; the eager drop-in path beside it).
+    # ---- decode (headline): M = 1, one launch per WOQ matmul (graph-replayed; with --full the eager drop-in path beside it).
     # Tensor parallel: the same launches on this rank's shards + C-ABI all-reduce after O and down.  (The round-3/4
     # weight-stream engine -- one persistent launch per segment -- stayed slower than these launches and left the
     # product in round 5: tools/engine/)
@@ -528,6 +562,34 @@ def main(argv=None):
     dec = Runner(stack, 1, pc, "cuda")
     dt = timed(dec, args.steps, args.warmup, use_graph)
     tok_s = args.steps / dt
+    if args.dump_outputs:
+        dump_outputs(dec, args.dump_outputs, rank, world)
+    line = {
+        "metric": METRIC,
+        "value": round(tok_s, 2),
+        "unit": "tokens/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(dt / args.steps * 1e3, 4),
+        "higher_is_better": True,
+        "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": "f16",
+        "data": "synthetic: random int4 codes + fp16 group scales U[0.001,0.01] in Llama-2-7B shapes (no checkpoint)",
+        "config": {"workload": "Llama-2-7B int4-g128 sym decode linear stack, M=1 (32 x [QKV, O, gate/up+SiLU*mul, "
+                               "down] + lm_head), fp32 activations", "group_size": LLAMA["group"], "batch": 1,
+                   "tp": world, "parallelism": f"tp{world}", "hip_graph": use_graph,
+                   "decode_path": "per-op launches"},
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if pc is not None:
+            pc.destroy()
+        return 0
+
+    # ---- everything below is --full only
     # the eager drop-in path (what ne_graph_compute does: one host call per WOQ node, no graph)
     dt_eager = timed(dec, args.steps, args.warmup, False)
     eager_tok_s = args.steps / dt_eager
@@ -576,23 +638,7 @@ def main(argv=None):
 
     if rank == 0:
         cpu = None if (args.no_cpu_baseline or world > 1) else cpu_baseline()
-        line = {
-            "metric": METRIC,
-            "value": round(tok_s, 2),
-            "unit": "tokens/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(dt / args.steps * 1e3, 4),
-            "higher_is_better": True,
-            "scaling": "strong",
-            "vs_baseline": None,
-            "dtype": "f16",
-            "data": "synthetic: random int4 codes + fp16 group scales U[0.001,0.01] in Llama-2-7B shapes (no checkpoint)",
-            "config": {"workload": "Llama-2-7B int4-g128 sym decode linear stack, M=1 (32 x [QKV, O, gate/up+SiLU*mul, "
-                                   "down] + lm_head), fp32 activations", "group_size": LLAMA["group"], "batch": 1,
-                       "tp": world, "parallelism": f"tp{world}", "hip_graph": use_graph,
-                       "decode_path": "per-op launches"},
+        line.update({
             "prefill_tflops": round(prefill_tflops, 2),
             "prefill_ms_per_2048_tokens": round(pdt / args.prefill_steps * 1e3, 3),
             "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
@@ -610,7 +656,7 @@ def main(argv=None):
             "synthetic": synthetic,
             "workloads": extra,
             "cpu_baseline": cpu,
-        }
+        })
         print(json.dumps(line), flush=True)
     if pc is not None:
         pc.destroy()

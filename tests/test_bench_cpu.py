@@ -38,6 +38,38 @@ def test_dry_run_tp8_shard_table():
         assert r["o_k_rows"] == r["q_cols"] and r["gate_up_cols"] == r["down_k_rows"]
 
 
+def test_full_and_dump_outputs_are_options(tmp_path):
+    """--full and --dump-outputs DIR parse; a dry run measures nothing and writes nothing."""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--full", "--dump-outputs", str(out), "--dry-run"], capture_output=True, text=True, env=env,
+                       timeout=120)
+    assert r.returncode == 0, r.stderr
+    assert json.loads(r.stdout.strip().splitlines()[-1])["world"] == 1
+    assert not out.exists()
+
+
+def test_dump_outputs_writes_float32_npy(tmp_path):
+    """dump_outputs writes every array of Runner.outputs() as <name>.npy in float32, whatever dtype the path computes
+    in, and tensor-parallel ranks keep their shards apart by name."""
+    import numpy as np
+    import torch
+
+    import bench
+
+    class FakeRunner:
+        def outputs(self):
+            return {"o": torch.arange(6, dtype=torch.float16).reshape(2, 3), "logits": torch.ones(1, 5)}
+
+    bench.dump_outputs(FakeRunner(), str(tmp_path / "a"), 0, 1)
+    assert sorted(os.listdir(tmp_path / "a")) == ["logits.npy", "o.npy"]
+    o = np.load(tmp_path / "a" / "o.npy")
+    assert o.dtype == np.float32 and o.shape == (2, 3) and np.array_equal(o.ravel(), np.arange(6, dtype=np.float32))
+    bench.dump_outputs(FakeRunner(), str(tmp_path / "b"), 3, 8)
+    assert sorted(os.listdir(tmp_path / "b")) == ["logits_rank3.npy", "o_rank3.npy"]
+
+
 def test_dry_run_single_gpu():
     d = _dry(1)
     assert not d["relaunch"] and d["world"] == 1

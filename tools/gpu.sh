@@ -3,7 +3,7 @@
 # that faults / aborts / times out (exit >= 124) ends the call, a plain test failure (1) does not.  Outputs go to
 # gpurun_out/<task>_$TAG.*.  Tasks:
 #   tests      pytest -m gpu (PYTEST_K filters)              smoke    __graft_entry__.smoke()
-#   bench      bench.py (STEPS, BENCH_ARGS)                  prof     rocprofv3 --kernel-trace --stats over a short bench
+#   bench      bench.py --full (STEPS, BENCH_ARGS)           prof     rocprofv3 --kernel-trace --stats over a short bench
 #   traffic    PMC FETCH_SIZE / WRITE_SIZE passes of the decode token (tools/pmc_decode.py -> tools/pmc_traffic.py)
 #   sq         SQ counter passes (PMC_SETS: ';'-separated, one run each) over PMC_CMD (default: the lm_head decode GEMV sweep),
 #              summarised per kernel with derived ratios (tools/pmc_derive.py)
@@ -27,13 +27,14 @@ for task in "$@"; do
     smoke)
       timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/smoke_$TAG.log 2>&1; rc=$?
       tail -5 gpurun_out/smoke_$TAG.log; echo "smoke rc=$rc"; [ $rc -eq 0 ] || exit $rc ;;
-    bench)
+    bench)  # the whole record (secondary figures included): bench.py --full
+      BENCH_ARGS="--full ${BENCH_ARGS}"
       timeout -k 10 600 python bench.py --steps ${STEPS:-30} --warmup 5 ${BENCH_ARGS} > gpurun_out/bench_$TAG.json \
         2> gpurun_out/bench_$TAG.err; rc=$?
       cat gpurun_out/bench_$TAG.json; tail -3 gpurun_out/bench_$TAG.err; echo "bench rc=$rc"; [ $rc -eq 0 ] || exit $rc ;;
     prof)
       timeout -k 10 600 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_$TAG -o run --output-format csv -- \
-        python bench.py --steps 10 --warmup 2 --prefill-steps 1 --no-cpu-baseline ${BENCH_ARGS} \
+        python bench.py --full --steps 10 --warmup 2 --prefill-steps 1 --no-cpu-baseline ${BENCH_ARGS} \
         > gpurun_out/prof_bench_$TAG.json 2> gpurun_out/prof_$TAG.err; rc=$?
       echo "rocprof rc=$rc"; [ $rc -eq 0 ] || exit $rc
       find gpurun_out/prof_$TAG -name "*kernel_stats.csv" | head -1 | xargs cut -d, -f1-8 | head -20 ;;
@@ -65,7 +66,7 @@ for task in "$@"; do
       f=gpurun_out/abbench_$TAG.txt; : > $f
       for r in $(seq ${ROUNDS:-3}); do for l in ${LIBS:-main}; do
         if [ "$l" = main ]; then p=neural_amd/libneural_amd.so; else p=neural_amd/libneural_amd_x$l.so; fi
-        NAD_LIB_PATH=$PWD/$p timeout -k 10 300 python bench.py --steps 30 --warmup 5 --prefill-steps 1 --no-cpu-baseline \
+        NAD_LIB_PATH=$PWD/$p timeout -k 10 300 python bench.py --full --steps 30 --warmup 5 --prefill-steps 1 --no-cpu-baseline \
           --no-extra --no-synthetic > gpurun_out/abbench_$l.json 2>/dev/null || exit 124
         python -c "import json,sys; d=json.load(open(sys.argv[1])); print(sys.argv[2], d['value'], d.get('decode_eager_tokens_per_s'), d['roofline']['avg_launch_us'], d.get('prefill_tflops'))" gpurun_out/abbench_$l.json $l | tee -a $f
       done; done ;;
