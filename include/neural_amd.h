@@ -242,7 +242,7 @@ int nad_get_compute_mode(void);
 /* per-thread override of the process mode (-1 clears it); thread-safe, takes precedence over nad_set_compute_mode */
 int nad_set_thread_compute_mode(int mode);
 /* per-weight arithmetic, as the reference selects it per blob core (bestla_gemm.cpp:516-616): -1 follow the
- * thread / process mode, 0 fp, 1 int8 (integer-core blobs and GGUF Q4_0; other weights stay fp).  Takes precedence
+ * thread / process mode, 0 fp, 1 int8 (integer-core blobs and the GGUF types; other weights stay fp).  Takes precedence
  * over both; a fused call whose weights resolve to different arithmetic runs each weight in its own. */
 int nad_device_set_compute(void* devstor, int mode);
 /* the arithmetic a forward of this weight takes now: 0 fp, 1 int8, -1 not a device weight */
@@ -260,6 +260,35 @@ size_t nad_q4_0_device_size(int n, int k);
 int nad_q4_0_device_load(const void* blocks, int n, int k, void* devstor, void* deviceptr, size_t capacity, void* queue);
 /* quantize_row_q8_0 (vectors/cpu/quantize.h:422-445) on device pointers: act [m][lda] -> m rows of K/32 block_q8_0 */
 int nad_quant_q8_0(const void* act, int act_dtype, int m, int k, int lda, void* blocks, void* queue);
+/* ===== the other legacy GGUF block types the reference matmuls (quantize_fns, neural_speed/core/ne_layers.c:266-318;
+ * blocks: core/data_types.h:79-118).  Type codes are the reference's ne_type values.  Q5_0 and Q8_0 load into the
+ * symmetric int8 layout, Q5_1 into the int8 layout and Q4_1 into the symmetric int4 layout (the nibble holds q, decoded as q - 8, and the finishing pass adds 8 d with the min); the fp16
+ * block minimum of Q4_1 / Q5_1 (w = q d + m) is kept in a region of its own and added by a finishing pass after the
+ * forward kernel (two launches per weight, three with the block-sum pre-pass above 16 rows), which also applies the
+ * epilogue.  Every nad_device_* / bestla_device_* forward accepts the descriptor.  nad_device_qkv_forward runs the
+ * three weights one after another when any carries mins; nad_device_ffn_gate_up / nad_device_ffn_forward run the gate
+ * and the up weight as two passes then, and a pair that mixes a min and a non-min weight WORKS as long as the two share
+ * the device format the entry requires anyway (bits, group size, scale type; e.g. Q5_1 + Q8_0); such a pair always
+ * takes the two-pass path, i.e. it gives up the single dual-weight decode launch of a pair without mins.
+ * nad_batch_create refuses a weight with mins (the batched GEMV has no finishing pass).  Compute mode 1
+ * reproduces the reference's integer arithmetic: Q8_0 activations for Q5_0 / Q8_0 (ne_vec_dot_q5_0_q8_0,
+ * ne_vec_dot_q8_0_q8_0), Q8_1 for Q4_1 / Q5_1 (ne_vec_dot_q4_1_q8_1, ne_vec_dot_q5_1_q8_1); a fused call whose weights
+ * need different activation quantizers fails with a recorded error.  NAD_GGUF_Q4_0 through these entries is
+ * nad_q4_0_* exactly. */
+#define NAD_GGUF_Q4_0 2
+#define NAD_GGUF_Q4_1 3
+#define NAD_GGUF_Q5_0 6
+#define NAD_GGUF_Q5_1 7
+#define NAD_GGUF_Q8_0 8
+/* bytes of one 32-element block: 18 / 20 / 22 / 24 / 34; 0 and an error naming the type otherwise */
+size_t nad_gguf_block_bytes(int type);
+/* device bytes of the matrix; 0 and nad_last_error() for an unsupported type or k % 32 != 0 */
+size_t nad_gguf_device_size(int type, int n, int k);
+int nad_gguf_device_load(int type, const void* blocks, int n, int k, void* devstor, void* deviceptr, size_t capacity,
+                         void* queue);
+/* quantize_row_q8_1_reference (vectors/cpu/quantize.h:546-579) on device pointers: act [m][lda] -> m rows of K/32
+ * blocks {float d; float s; int8 qs[32]} */
+int nad_quant_q8_1(const void* act, int act_dtype, int m, int k, int lda, void* blocks, void* queue);
 /* host convenience: (re)pack one blob into fp32 dequantized [K][N] from the device tile layout (round-trip check) */
 int nad_device_unpack_fp32(const void* devstor, float* host_out, void* queue);
 

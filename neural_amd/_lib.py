@@ -92,6 +92,10 @@ SIGNATURES = {
     "nad_q4_0_device_size": (_sz, [_i, _i]),
     "nad_q4_0_device_load": (_i, [_p, _i, _i, _p, _p, _sz, _p]),
     "nad_quant_q8_0": (_i, [_p, _i, _i, _i, _i, _p, _p]),
+    "nad_gguf_block_bytes": (_sz, [_i]),
+    "nad_gguf_device_size": (_sz, [_i, _i, _i]),
+    "nad_gguf_device_load": (_i, [_i, _p, _i, _i, _p, _p, _sz, _p]),
+    "nad_quant_q8_1": (_i, [_p, _i, _i, _i, _i, _p, _p]),
     "nad_batch_create": (_p, [_p, _i]),
     "nad_batch_run": (_i, [_p, _p]),
     "nad_batch_destroy": (None, [_p]),

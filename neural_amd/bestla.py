@@ -263,6 +263,26 @@ class DeviceWeight:
         check(L.nad_q4_0_device_load(_ptr(blocks), n, k, desc, _ptr(mem), need, _stream(stream)), "nad_q4_0_device_load")
         return cls(_desc=desc, _mem=mem)
 
+    @classmethod
+    def from_gguf(cls, type, blocks, n, k, device=None, stream=None):
+        """A GGUF matrix of one of the legacy block types (GGUF_Q4_0 / Q4_1 / Q5_0 / Q5_1 / Q8_0: n rows of k/32 blocks,
+        as an ne_tensor of that NE_TYPE holds it) in the device tile layout (nad_gguf_device_load)."""
+        torch = _torch()
+        L = lib()
+        bb = L.nad_gguf_block_bytes(int(type))
+        if not bb:
+            raise RuntimeError(last_error())
+        blocks = np.ascontiguousarray(blocks, dtype=np.uint8)
+        assert blocks.size == n * (k // 32) * bb, (blocks.size, n, k, bb)
+        need = L.nad_gguf_device_size(int(type), n, k)
+        if not need:
+            raise RuntimeError(last_error())
+        mem = torch.empty(need, dtype=torch.uint8, device=device or "cuda")
+        desc = (C.c_uint8 * L.bestla_device_storage_size())()
+        check(L.nad_gguf_device_load(int(type), _ptr(blocks), n, k, desc, _ptr(mem), need, _stream(stream)),
+              "nad_gguf_device_load")
+        return cls(_desc=desc, _mem=mem)
+
     def forward(self, x, out=None, epilogue=EPI_NONE, bias=None, residual=None, stream=None):
         """out[m][n] = epi(sum_k x[m][k] * W[n][k]); x: cuda [M][K] fp32/fp16/bf16 (row stride honoured)."""
         torch = _torch()
@@ -290,7 +310,7 @@ class DeviceWeight:
 
     def set_compute(self, mode):
         """Per-weight arithmetic (nad_device_set_compute): None / -1 follow the thread / process mode, COMPUTE_FP or
-        COMPUTE_INT8 (integer-core blobs and GGUF Q4_0 only; other weights stay fp)."""
+        COMPUTE_INT8 (integer-core blobs and GGUF matrices only; other weights stay fp)."""
         check(lib().nad_device_set_compute(self.desc, -1 if mode is None else int(mode)), "nad_device_set_compute")
         return self
 
@@ -307,6 +327,8 @@ class DeviceWeight:
 
 
 COMPUTE_FP, COMPUTE_INT8 = 0, 1
+# GGUF block types (the reference's ne_type values, neural_speed/core/data_types.h)
+GGUF_Q4_0, GGUF_Q4_1, GGUF_Q5_0, GGUF_Q5_1, GGUF_Q8_0 = 2, 3, 6, 7, 8
 
 
 def set_compute_mode(mode):
@@ -348,6 +370,16 @@ def quant_q8_0(x, stream=None):
     m, k = x.shape
     out = torch.empty((m, k // 32 * 34), dtype=torch.uint8, device=x.device)
     check(lib().nad_quant_q8_0(_ptr(x), _act_code(x), m, k, x.stride(0), _ptr(out), _stream(stream)), "nad_quant_q8_0")
+    return out
+
+
+def quant_q8_1(x, stream=None):
+    """quantize_row_q8_1_reference (vectors/cpu/quantize.h:546-579) on the GPU: x cuda [M][K] -> uint8 [M][K/32 * 40]
+    blocks {float d; float s; int8 qs[32]}"""
+    torch = _torch()
+    m, k = x.shape
+    out = torch.empty((m, k // 32 * 40), dtype=torch.uint8, device=x.device)
+    check(lib().nad_quant_q8_1(_ptr(x), _act_code(x), m, k, x.stride(0), _ptr(out), _stream(stream)), "nad_quant_q8_1")
     return out
 
 

@@ -527,7 +527,7 @@ static int try_gemv(const void* act, int act_t, int lda, int m, int k, int nw, c
 }
 
 static bool int8_compute(const DeviceWeight& w);
-static bool is_q4_0(const DeviceWeight& w);
+static int gguf_act_quant(const DeviceWeight& w);
 static int run_i8(const void* act, int act_t, int lda, int m, int k, int nw, const DeviceWeight* const* ws,
                   float* const* outs, const int* ldos, bool dual, int epi, const float* bias, int bias_ld,
                   const float* res, int ld_res, const float* aux, int ld_aux, hipStream_t st);
@@ -538,7 +538,7 @@ static int run_skinny(const void* act, int act_t, int lda, int m, int k, int nw,
   if (nw > 1) {  // weights of one fused call whose arithmetic differs (per-weight compute modes) run one by one
     bool mixed = false;
     for (int i = 1; i < nw; i++)
-      mixed |= int8_compute(*ws[i]) != int8_compute(*ws[0]) || is_q4_0(*ws[i]) != is_q4_0(*ws[0]);
+      mixed |= int8_compute(*ws[i]) != int8_compute(*ws[0]) || gguf_act_quant(*ws[i]) != gguf_act_quant(*ws[0]);
     if (mixed) {
       if (epi == kEpiSiluMul || epi == kEpiGeluMul) {
         set_err("gate/up weights of one FFN must resolve to the same arithmetic (nad_device_set_compute)");
@@ -662,7 +662,8 @@ static void* workspace_for(size_t bytes, hipStream_t st) {
 // The arithmetic is chosen per call, in order: the weight's own setting (nad_device_set_compute: the reference picks
 // it per blob core, bestla_gemm.cpp:516-616), else the calling thread's (nad_set_thread_compute_mode), else the
 // process default (nad_set_compute_mode, initialised from NAD_COMPUTE_INT8).  Mode 1 applies to blobs packed for an
-// integer core only -- exactly those that carry the reduce -- and to GGUF Q4_0; every other weight stays fp.
+// integer core only -- exactly those that carry the reduce -- and to the GGUF block types (Q4_0, Q4_1, Q5_0, Q5_1,
+// Q8_0: the reference's Q8_0 / Q8_1 vec_dot arithmetic); every other weight stays fp.
 static std::atomic<int> g_compute_mode{-1};
 static thread_local int t_compute_mode = -1;
 static int compute_mode() {
@@ -678,9 +679,31 @@ static int compute_mode() {
 // a GGUF Q4_0 matrix (nad_q4_0_device_load) carries this in src_core_id: its int8 arithmetic is Q8_0 x Q4_0
 constexpr uint64_t kGgufQ4_0 = 0x3054344655474700ull;  // "\0GGUF4Q0"
 static bool is_q4_0(const DeviceWeight& w) { return w.src_core_id == kGgufQ4_0; }
+// the other GGUF block types (nad_gguf_device_load): the same tag with the type's two characters
+constexpr uint64_t kGgufQ4_1 = 0x3154344655474700ull;  // "\0GGUF4Q1"
+constexpr uint64_t kGgufQ5_0 = 0x3054354655474700ull;  // "\0GGUF5Q0"
+constexpr uint64_t kGgufQ5_1 = 0x3154354655474700ull;  // "\0GGUF5Q1"
+constexpr uint64_t kGgufQ8_0 = 0x3054384655474700ull;  // "\0GGUF8Q0"
+// NAD_GGUF_* of a loaded weight, 0 for a weight that is no GGUF matrix
+static int gguf_type(const DeviceWeight& w) {
+  if (is_q4_0(w)) return NAD_GGUF_Q4_0;
+  switch (w.src_core_id) {
+    case kGgufQ4_1: return NAD_GGUF_Q4_1;
+    case kGgufQ5_0: return NAD_GGUF_Q5_0;
+    case kGgufQ5_1: return NAD_GGUF_Q5_1;
+    case kGgufQ8_0: return NAD_GGUF_Q8_0;
+    default: return 0;
+  }
+}
+// the activation quantizer of the weight's int8 arithmetic (its vec_dot_type, ne_layers.c:266-318): 0 the kblock
+// core's u8, 1 Q8_0 (Q4_0, Q5_0, Q8_0), 2 Q8_1 (Q4_1, Q5_1)
+static int gguf_act_quant(const DeviceWeight& w) {
+  const int t = gguf_type(w);
+  return t == 0 ? 0 : ((t == NAD_GGUF_Q4_1 || t == NAD_GGUF_Q5_1) ? 2 : 1);
+}
 static int effective_mode(const DeviceWeight& w) { return w.compute > 0 ? w.compute - 1 : compute_mode(); }
 static bool int8_compute(const DeviceWeight& w) {
-  return effective_mode(w) == 1 && (w.reduce != nullptr || is_q4_0(w));
+  return effective_mode(w) == 1 && (w.reduce != nullptr || gguf_type(w) != 0);
 }
 
 extern "C" int nad_set_compute_mode(int mode) {
@@ -736,7 +759,7 @@ static size_t i8_act_bytes(int m, const DeviceWeight& w) {
 static int i8_quantize(I8Act& r, char* ws, const void* act, int act_t, int lda, int m, int k, const DeviceWeight& w,
                        hipStream_t st) {
   const int kp = w.nt * tile_k(w.bits);
-  if (is_q4_0(w)) {  // Q8_0 rows (quantize_row_q8_0_reference)
+  if (gguf_act_quant(w)) {  // Q8_0 / Q8_1 rows (quantize_row_q8_0_reference / quantize_row_q8_1_reference)
     Q80Args q{};
     q.A = act;
     q.lda = lda;
@@ -746,9 +769,11 @@ static int i8_quantize(I8Act& r, char* ws, const void* act, int act_t, int lda, 
     q.ldq = kp;
     q.kp = kp;
     q.sa = reinterpret_cast<float2*>(ws + align256(size_t(m) * kp));
-    hipError_t e = planned(0, 0, 0, 1, 0, false) ? hipSuccess : launch_q8_0_quant(q, act_t, st);
+    hipError_t e = planned(0, 0, 0, 1, 0, false)
+                       ? hipSuccess
+                       : (gguf_act_quant(w) == 2 ? launch_q8_1_quant(q, act_t, st) : launch_q8_0_quant(q, act_t, st));
     if (e != hipSuccess) {
-      set_err("Q8_0 activation quantization launch failed: %s", hipGetErrorString(e));
+      set_err("Q8_0 / Q8_1 activation quantization launch failed: %s", hipGetErrorString(e));
       return -1;
     }
     r.aq = q.aq;
@@ -779,13 +804,17 @@ static int i8_quantize(I8Act& r, char* ws, const void* act, int act_t, int lda, 
   return 0;
 }
 
-static int i8_gemm(const I8Act& x, int m, int k, const DeviceWeight& w, float* out, int ldo, int epi,
-                   const float* bias, int bias_ld, const float* res, int ld_res, const float* aux, int ld_aux,
-                   hipStream_t st) {
+static int min_term(const void* act, int act_t, int lda, const float* S, int s_ld, int s_st, int m, int k,
+                    const DeviceWeight& w, float* out, int ldo, int epi, const float* bias, int bias_ld,
+                    const float* res, int ld_res, const float* aux, int ld_aux, hipStream_t st);
+
+static int i8_gemm_main(const I8Act& x, int m, int k, const DeviceWeight& w, float* out, int ldo, int epi,
+                        const float* bias, int bias_ld, const float* res, int ld_res, const float* aux, int ld_aux,
+                        hipStream_t st) {
   I8Args a{};
   a.aq = x.aq;
   a.ldq = x.ldq;
-  a.a_signed = is_q4_0(w) ? 1 : 0;
+  a.a_signed = gguf_act_quant(w) ? 1 : 0;
   a.sa = x.sa;
   a.M = m;
   a.K = k;
@@ -806,14 +835,26 @@ static int i8_gemm(const I8Act& x, int m, int k, const DeviceWeight& w, float* o
   return 0;
 }
 
+static int i8_gemm(const I8Act& x, int m, int k, const DeviceWeight& w, float* out, int ldo, int epi,
+                   const float* bias, int bias_ld, const float* res, int ld_res, const float* aux, int ld_aux,
+                   hipStream_t st) {
+  if (!w.mins) return i8_gemm_main(x, m, k, w, out, ldo, epi, bias, bias_ld, res, ld_res, aux, ld_aux, st);
+  // Q4_1 / Q5_1 x Q8_1 (vec_dot.h:385-400, 569-590): the block dots on the true q, then + sum_b m * s with the Q8_1
+  // block sums s = sa[].y, and the caller's epilogue
+  if (i8_gemm_main(x, m, k, w, out, ldo, kEpiNone, nullptr, 0, nullptr, 0, nullptr, 0, st)) return -1;
+  return min_term(nullptr, kActF32, 0, &x.sa[0].y, 2 * w.ng, 2, m, k, w, out, ldo, epi, bias, bias_ld, res, ld_res, aux,
+                  ld_aux, st);
+}
+
 // nw weights on one activation.  dual: the FFN gate/up pair (outs[1] = act(x.w0) * (x.w1); aux, if given, receives
 // act(x.w0)), run as the prefill FFN does: two passes, the second multiplying by the first's output.
 static int run_i8(const void* act, int act_t, int lda, int m, int k, int nw, const DeviceWeight* const* ws,
                   float* const* outs, const int* ldos, bool dual, int epi, const float* bias, int bias_ld,
                   const float* res, int ld_res, const float* aux, int ld_aux, hipStream_t st) {
   for (int i = 0; i < nw; i++)
-    if (!int8_compute(*ws[i]) || is_q4_0(*ws[i]) != is_q4_0(*ws[0])) {
-      set_err("int8 compute: the weights of a fused call must all be integer-core blobs (with reduce) or all Q4_0");
+    if (!int8_compute(*ws[i]) || gguf_act_quant(*ws[i]) != gguf_act_quant(*ws[0])) {
+      set_err("int8 compute: the weights of a fused call must all be integer-core blobs (with reduce) or all GGUF types "
+              "of one activation quantizer (Q8_0: Q4_0, Q5_0, Q8_0; Q8_1: Q4_1, Q5_1)");
       return -1;
     }
   const size_t abytes = i8_act_bytes(m, *ws[0]);
@@ -832,6 +873,58 @@ static int run_i8(const void* act, int act_t, int lda, int m, int k, int nw, con
   }
   for (int i = 0; i < nw; i++)
     if (i8_gemm(x, m, k, *ws[i], outs[i], ldos[i], epi, bias, bias_ld, res, ld_res, aux, ld_aux, st)) return -1;
+  return 0;
+}
+
+// The minimum term of a GGUF Q4_1 / Q5_1 weight and the caller's epilogue, on an `out` that holds X (q d)^T
+// (woq_gguf.hip): out = epi(out + S mins^T).  S null: the exact block sums of the activations -- summed inside the
+// M <= 16 kernel, else by a pre-pass into the workspace (the main kernel's use of it is over by stream order).  A
+// weight without mins gets the epilogue alone (the mixed FFN pairs).
+static int min_term(const void* act, int act_t, int lda, const float* S, int s_ld, int s_st, int m, int k,
+                    const DeviceWeight& w, float* out, int ldo, int epi, const float* bias, int bias_ld,
+                    const float* res, int ld_res, const float* aux, int ld_aux, hipStream_t st) {
+  MinTermArgs a{};
+  a.A = act;
+  a.lda = lda;
+  a.M = m;
+  a.K = k;
+  a.S = S;
+  a.s_ld = s_ld;
+  a.s_st = s_st;
+  a.mins = static_cast<const uint16_t*>(w.mins);
+  a.scales = static_cast<const uint16_t*>(w.scales);  // GGUF: fp16
+  a.qbias = float(w.min_bias);
+  a.ns = w.ns;
+  a.ng = w.ng;
+  a.kmajor = w.kmajor;
+  a.g.M = m;
+  a.g.K = k;
+  a.g.epi = epi == kEpiGeluMul ? kEpiSiluMul : epi;  // the multiply by aux (the activation is in aux already)
+  a.g.res = res;
+  a.g.ld_res = ld_res;
+  a.g.aux = aux;
+  a.g.ld_aux = ld_aux;
+  a.g.w = view(w, out, ldo, bias, bias_ld);
+  const bool small = m <= kMinTermSmallM && size_t(m) * w.ng * sizeof(float) <= kMinTermSmallLds;
+  if (!small && a.mins && !S) {
+    float* sums = static_cast<float*>(workspace_for(size_t(m) * w.ng * sizeof(float), st));
+    if (!sums) return -1;
+    const hipError_t e = planned(0, 0, 0, 1, 0, false) ? hipSuccess : launch_block_sums(act, act_t, lda, m, k, sums, st);
+    if (e != hipSuccess) {
+      set_err("activation block-sum launch failed: %s", hipGetErrorString(e));
+      return -1;
+    }
+    a.S = sums;
+    a.s_ld = w.ng;
+    a.s_st = 1;
+  }
+  const hipError_t e = planned(0, 0, 0, 1, 0, false)
+                           ? hipSuccess
+                           : (small ? launch_min_term(a, act_t, st) : launch_min_term_tiled(a, st));
+  if (e != hipSuccess) {
+    set_err("min-term kernel launch failed: %s", hipGetErrorString(e));
+    return -1;
+  }
   return 0;
 }
 
@@ -931,6 +1024,131 @@ extern "C" int nad_quant_q8_0(const void* act, int act_dtype, int m, int k, int 
   hipError_t e = launch_q8_0_quant(a, act_dtype, static_cast<hipStream_t>(queue));
   if (e != hipSuccess) {
     set_err("Q8_0 quantization launch failed: %s", hipGetErrorString(e));
+    return -1;
+  }
+  return 0;
+}
+
+// ------------------------------------------------------------------------------- GGUF Q4_1 / Q5_0 / Q5_1 / Q8_0
+extern "C" size_t nad_gguf_block_bytes(int type) {
+  switch (type) {
+    case NAD_GGUF_Q4_0: return 18;
+    case NAD_GGUF_Q4_1: return 20;
+    case NAD_GGUF_Q5_0: return 22;
+    case NAD_GGUF_Q5_1: return 24;
+    case NAD_GGUF_Q8_0: return 34;
+    default:
+      set_err("GGUF type %d is not supported (Q4_0 = 2, Q4_1 = 3, Q5_0 = 6, Q5_1 = 7, Q8_0 = 8)", type);
+      return 0;
+  }
+}
+
+// geometry of a GGUF matrix of the four new types: Q4_1 in the symmetric int4 layout, the others in the symmetric int8
+// layout; the fp16 mins of Q4_1 / Q5_1 follow the layout's own regions
+static uint64_t gguf_geometry(DeviceWeight& w, int type, int n, int k, uint64_t* mins_off) {
+  const bool q41 = type == NAD_GGUF_Q4_1;
+  const uint64_t base = layout_geometry(w, q41 ? 4 : 8, n, k, 32, kScaleF16, false, false);
+  const bool has_m = q41 || type == NAD_GGUF_Q5_1;
+  if (mins_off) *mins_off = base;
+  return base + (has_m ? align256(uint64_t(w.ns) * w.ng * 16 * 2) : 0);
+}
+
+extern "C" size_t nad_gguf_device_size(int type, int n, int k) {
+  if (!nad_gguf_block_bytes(type)) return 0;
+  if (type == NAD_GGUF_Q4_0) return nad_q4_0_device_size(n, k);
+  if (n <= 0 || k <= 0 || k % 32) {
+    set_err("a GGUF matrix needs n > 0 and k a positive multiple of 32 (type=%d n=%d k=%d)", type, n, k);
+    return 0;
+  }
+  DeviceWeight w{};
+  return gguf_geometry(w, type, n, k, nullptr);
+}
+
+extern "C" int nad_gguf_device_load(int type, const void* blocks, int n, int k, void* devstor, void* deviceptr,
+                                    size_t capacity, void* queue) {
+  const size_t bb = nad_gguf_block_bytes(type);
+  if (!bb) return -1;
+  if (type == NAD_GGUF_Q4_0) return nad_q4_0_device_load(blocks, n, k, devstor, deviceptr, capacity, queue);
+  const size_t need = nad_gguf_device_size(type, n, k);
+  if (!need) return -1;
+  if (!blocks || !devstor || !deviceptr || capacity < need) {
+    set_err("nad_gguf_device_load: null pointer or device buffer too small (need %zu, have %zu)", need, capacity);
+    return -1;
+  }
+  hipStream_t st = static_cast<hipStream_t>(queue);
+  DeviceWeight w{};
+  uint64_t mins_off = 0;
+  const uint64_t total = gguf_geometry(w, type, n, k, &mins_off);
+  layout_assign(w, deviceptr);
+  const bool has_m = total > mins_off;
+  if (has_m) {
+    w.mins = static_cast<char*>(deviceptr) + mins_off;
+    w.bytes = total;
+    w.min_bias = type == NAD_GGUF_Q4_1 ? 8 : 0;  // the nibble holds q, the layout decodes q - 8
+  }
+  w.owner = nullptr;
+  w.src_core_id = type == NAD_GGUF_Q4_1 ? kGgufQ4_1
+                  : type == NAD_GGUF_Q5_0 ? kGgufQ5_0
+                  : type == NAD_GGUF_Q5_1 ? kGgufQ5_1
+                                          : kGgufQ8_0;
+  {  // every block starts with the fp16 d; the largest |decoded value| of the type
+    const float qmax = type == NAD_GGUF_Q4_1 ? 8.f : (type == NAD_GGUF_Q5_0 ? 16.f : (type == NAD_GGUF_Q5_1 ? 31.f : 128.f));
+    const uint8_t* bp = static_cast<const uint8_t*>(blocks);
+    bool ok = true;
+    for (size_t i = 0; ok && i < size_t(n) * (k / 32); i++) {
+      uint16_t h;
+      std::memcpy(&h, bp + bb * i, 2);
+      ok = scale_in_fold_range(float(__builtin_bit_cast(_Float16, h)), qmax);
+    }
+    w.fold_ok = ok ? 1 : 0;
+  }
+  // padding columns / K tiles decode to 0: int8 byte 128, nibble 8; scale 0, min 0
+  const size_t entries = size_t(w.ns) * w.ng * 16;
+  HIP_OK(hipMemsetAsync(w.tiles, w.bits == 4 ? 0x88 : 0x80, size_t(w.ns) * w.nt * 1024, st));
+  HIP_OK(hipMemsetAsync(w.scales, 0, entries * 2, st));
+  if (w.mins) HIP_OK(hipMemsetAsync(w.mins, 0, entries * 2, st));
+  const size_t bytes = size_t(n) * (k / 32) * bb;
+  uint8_t* stage = nullptr;
+  HIP_OK(hipMalloc(&stage, bytes));
+  // copy, repack, wait; the staging buffer is freed on every way out
+  const char* what = "hipMemcpyAsync of the blocks";
+  hipError_t e = hipMemcpyAsync(stage, blocks, bytes, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) {
+    what = "GGUF repack launch";
+    e = launch_gguf_repack(type, stage, n, k, w, st);
+  }
+  const hipError_t es = hipStreamSynchronize(st);  // also after a failure: the copy may still read `blocks`
+  if (e == hipSuccess && es != hipSuccess) {
+    what = "hipStreamSynchronize";
+    e = es;
+  }
+  const hipError_t ef = hipFree(stage);
+  if (e == hipSuccess && ef != hipSuccess) {
+    what = "hipFree of the staging buffer";
+    e = ef;
+  }
+  if (e != hipSuccess) {
+    set_err("nad_gguf_device_load: %s failed: %s", what, hipGetErrorString(e));
+    return -1;
+  }
+  std::memcpy(devstor, &w, sizeof(w));
+  return 0;
+}
+
+extern "C" int nad_quant_q8_1(const void* act, int act_dtype, int m, int k, int lda, void* blocks, void* queue) {
+  if (m <= 0 || k <= 0 || k % 32 || lda < k || !blocks) {
+    set_err("nad_quant_q8_1: bad arguments (m=%d k=%d lda=%d)", m, k, lda);
+    return -1;
+  }
+  Q81Args a{};
+  a.A = act;
+  a.lda = lda;
+  a.M = m;
+  a.K = k;
+  a.blocks = static_cast<int8_t*>(blocks);
+  hipError_t e = launch_q8_1_quant(a, act_dtype, static_cast<hipStream_t>(queue));
+  if (e != hipSuccess) {
+    set_err("Q8_1 quantization launch failed: %s", hipGetErrorString(e));
     return -1;
   }
   return 0;
@@ -1287,6 +1505,12 @@ static bool check_shape(const DeviceWeight& w, int m, int n, int k, int lda, int
   return true;
 }
 
+static int forward_one(const void* act, int act_dtype, int lda, int m, int k, const DeviceWeight& w, float* out,
+                       int ldo, int epi, const float* bias, int bias_ld, const float* res, int ld_res, hipStream_t st);
+static int forward_min(const void* act, int act_dtype, int lda, int m, int k, const DeviceWeight& w, float* out,
+                       int ldo, int epi, const float* bias, int bias_ld, const float* res, int ld_res,
+                       const float* aux, int ld_aux, hipStream_t st);
+
 extern "C" int nad_device_forward(const void* act, int act_dtype, const void* devstor, float* out, int m, int n, int k,
                                   int lda, int ldo, int epi, const float* bias, int bias_ld, const float* res,
                                   int ld_res, void* queue) {
@@ -1301,6 +1525,16 @@ extern "C" int nad_device_forward(const void* act, int act_dtype, const void* de
     return -1;
   }
   hipStream_t st = static_cast<hipStream_t>(queue);
+  if (w->mins)
+    return forward_min(act, act_dtype, lda, m, k, *w, out, ldo, epi, bias, bias_ld, res, ld_res, nullptr, 0, st);
+  return forward_one(act, act_dtype, lda, m, k, *w, out, ldo, epi, bias, bias_ld, res, ld_res, st);
+}
+
+// one weight, one launch chain: the body of nad_device_forward
+static int forward_one(const void* act, int act_dtype, int lda, int m, int k, const DeviceWeight& wr, float* out,
+                       int ldo, int epi, const float* bias, int bias_ld, const float* res, int ld_res,
+                       hipStream_t st) {
+  const DeviceWeight* w = &wr;
   if (m <= kSkinnyMaxM) {
     // the mid-M kernel from 12 rows of fp16 activations / 8 of fp32 / bf16 (NAD_MID_MIN_M); below that, and for the
     // fused QKV / FFN entries at any M <= 16, the skinny GEMV.  Its split-K slabs fit nad_device_workspace_size(m, k).
@@ -1315,6 +1549,24 @@ extern "C" int nad_device_forward(const void* act, int act_dtype, const void* de
     return run_skinny(act, act_dtype, lda, m, k, 1, ws, outs, ldos, epi, bias, bias_ld, res, ld_res, nullptr, 0, st);
   }
   return run_gemm(act, act_dtype, lda, m, k, *w, out, ldo, epi, bias, bias_ld, res, ld_res, nullptr, 0, st);
+}
+
+// A weight with block mins (GGUF Q4_1 / Q5_1), or the partner of one in a fused FFN: the unchanged kernels compute
+// X (q d)^T into out, the min-term pass adds S mins^T and applies the epilogue (aux: the SILU_MUL / GELU_MUL operand).
+// In the int8 mode the Q8_1 sums replace S and run_i8 appends the pass itself.
+static int forward_min(const void* act, int act_dtype, int lda, int m, int k, const DeviceWeight& w, float* out,
+                       int ldo, int epi, const float* bias, int bias_ld, const float* res, int ld_res,
+                       const float* aux, int ld_aux, hipStream_t st) {
+  if (int8_compute(w)) {
+    const DeviceWeight* ws[1] = {&w};
+    float* outs[1] = {out};
+    const int ldos[1] = {ldo};
+    const int e = epi == kEpiGeluMul ? kEpiSiluMul : epi;
+    return run_i8(act, act_dtype, lda, m, k, 1, ws, outs, ldos, false, e, bias, bias_ld, res, ld_res, aux, ld_aux, st);
+  }
+  if (forward_one(act, act_dtype, lda, m, k, w, out, ldo, kEpiNone, nullptr, 0, nullptr, 0, st)) return -1;
+  return min_term(act, act_dtype, lda, nullptr, 0, 0, m, k, w, out, ldo, epi, bias, bias_ld, res, ld_res, aux, ld_aux,
+                  st);
 }
 
 extern "C" void bestla_device_f32f32_forward(float* activation, void* weiptr, float* output, int _m, int _n, int _k,
@@ -1439,6 +1691,17 @@ extern "C" int nad_device_qkv_forward(const void* act, int act_dtype, const void
   hipStream_t st = static_cast<hipStream_t>(queue);
   float* outs[3] = {oq, okk, ov};
   int ldos[3] = {ldo_q, ldo_k, ldo_v};
+  if (ws[0]->mins || ws[1]->mins || ws[2]->mins) {  // block mins: the three weights one after another
+    for (int i = 0; i < 3; i++) {
+      const DeviceWeight& w = *ws[i];
+      const int rc = w.mins ? forward_min(act, act_dtype, lda, m, k, w, outs[i], ldos[i], kEpiNone, nullptr, 0, nullptr,
+                                          0, nullptr, 0, st)
+                            : forward_one(act, act_dtype, lda, m, k, w, outs[i], ldos[i], kEpiNone, nullptr, 0, nullptr,
+                                          0, st);
+      if (rc) return -1;
+    }
+    return 0;
+  }
   if (m <= kSkinnyMaxM) {
     // one stream launch over every run of consecutive weights of one kind (Q, K and V may differ in N; a mixed-format
     // model such as the int2 policy's int4 wv gets {Q, K} + {V}), each output computed exactly as on its own
@@ -1523,6 +1786,35 @@ extern "C" int nad_device_ffn_gate_up(const void* act, int act_dtype, const void
     return -1;
   }
   hipStream_t st = static_cast<hipStream_t>(queue);
+  if (w1->mins || w3->mins) {
+    // block mins: two passes as run_i8's -- t1 = act(x.w1), tmp2 = t1 * (x.w3) -- each a main launch and the min-term
+    // pass, which applies the activation / the multiply.  Without tmp1, t1 lies in the workspace behind the part the
+    // passes' own kernels use (nad_device_workspace_size).
+    if (int8_compute(*w1) != int8_compute(*w3) ||
+        (int8_compute(*w1) && gguf_act_quant(*w1) != gguf_act_quant(*w3))) {
+      set_err("gate/up weights of one FFN must resolve to the same arithmetic (nad_device_set_compute) and, in the "
+              "int8 mode, to one activation quantizer");
+      return -1;
+    }
+    float* t1 = tmp1;
+    if (!t1) {
+      const size_t head = align256(nad_device_workspace_size(m, fin));
+      char* wsp = static_cast<char*>(workspace_for(head + size_t(m) * fmid * sizeof(float), st));
+      if (!wsp) return -1;
+      t1 = reinterpret_cast<float*>(wsp + head);
+    }
+    const int e1 = epi == kEpiSiluMul ? kEpiSilu : kEpiGelu;
+    // the partner without mins of a mixed pair applies the epilogue in its own kernel where that kernel can: the
+    // activation always, the multiply by t1 in the prefill GEMMs and the int8 kernel (the M <= 16 fp kernels take the
+    // multiply only as a fused pair, so there the min-term kernel runs as the epilogue alone)
+    const int r1 = w1->mins ? forward_min(act, act_dtype, lda, m, fin, *w1, t1, fmid, e1, nullptr, 0, nullptr, 0, nullptr,
+                                          0, st)
+                            : forward_one(act, act_dtype, lda, m, fin, *w1, t1, fmid, e1, nullptr, 0, nullptr, 0, st);
+    if (r1) return -1;
+    if (!w3->mins && m > kSkinnyMaxM)
+      return run_gemm(act, act_dtype, lda, m, fin, *w3, tmp2, fmid, kEpiSiluMul, nullptr, 0, nullptr, 0, t1, fmid, st);
+    return forward_min(act, act_dtype, lda, m, fin, *w3, tmp2, fmid, kEpiSiluMul, nullptr, 0, nullptr, 0, t1, fmid, st);
+  }
   if (m <= kSkinnyMaxM) {
     const DeviceWeight* ws[2] = {w1, w3};
     float* outs[2] = {tmp2, tmp2};
@@ -1565,7 +1857,8 @@ static int ffn_forward(const void* act, int act_dtype, const void* w1p, const vo
     return -1;
   }
   hipStream_t st = static_cast<hipStream_t>(queue);
-  if (f16_tmp && m > kSkinnyMaxM && tmp1 && ffn16_ok(*w1, *w2, *w3, m, fmid)) {
+  const bool any_mins = w1->mins || w2->mins || w3->mins;
+  if (!any_mins && f16_tmp && m > kSkinnyMaxM && tmp1 && ffn16_ok(*w1, *w2, *w3, m, fmid)) {
     // prefill with fp16 intermediates: gate -> act(x.w1) as fp16 in tmp1, up -> act(x.w1) * (x.w3) as fp16 in tmp2,
     // which IS down's fp16 A operand (fmid = whole K tiles): no fp32 round trip, no conversion pass before down
     A16 pre;
@@ -1586,6 +1879,8 @@ static int ffn_forward(const void* act, int act_dtype, const void* w1p, const vo
     return run_gemm(h2, kActF16, fmid, m, fmid, *w2, out, fout, kEpiNone, nullptr, 0, nullptr, 0, nullptr, 0, st, &d);
   }
   if (nad_device_ffn_gate_up(act, act_dtype, w1p, w3p, tmp1, tmp2, m, fin, fmid, lda, epi, queue)) return -1;
+  if (w2->mins)
+    return forward_min(tmp2, kActF32, fmid, m, fmid, *w2, out, fout, kEpiNone, nullptr, 0, nullptr, 0, nullptr, 0, st);
   if (m <= kSkinnyMaxM) {
     const DeviceWeight* ws[1] = {w2};
     float* outs[1] = {out};
@@ -1628,6 +1923,10 @@ extern "C" void* nad_batch_create(const nad_batch_problem* p, int n) {
     }
     if (w->shuffle || int8_compute(*w)) {
       set_err("nad_batch_create: act-order and int8-compute weights are not batched");
+      return nullptr;
+    }
+    if (w->mins) {  // the batched GEMV has no min-term pass: it would drop S (m + bias d)^T
+      set_err("nad_batch_create: problem %d's weight carries block mins (GGUF Q4_1 / Q5_1), which are not batched", i);
       return nullptr;
     }
     if (!p[i].act || !p[i].out || reinterpret_cast<uintptr_t>(p[i].act) % 16 != 0) {
@@ -1826,7 +2125,10 @@ __global__ void nad_unrepack_kernel(DeviceWeight w, float* out) {
     } else {
       q = w.f4kind >= 0 ? kF4LutF[w.f4kind][v & 15] : float(int(v) - bias - zp);
     }
-    out[i] = q * sc;
+    if (w.mins) q = q + float(w.min_bias);  // Q4_1 / Q5_1: the true q, q d exact, + m rounded once
+    float r = q * sc;
+    if (w.mins) r = r + float(static_cast<const _Float16*>(w.mins)[si]);
+    out[i] = r;
   }
 }
 

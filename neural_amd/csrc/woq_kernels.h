@@ -203,7 +203,34 @@ struct Q80Args {
   float2* sa;           // [M][K/32] {float(fp16 d), 0}
   int8_t* blocks;       // optional raw block_q8_0 rows [M][K/32][34]
 };
+// Q8_1 activations (quantize_row_q8_1_reference): as Q80Args with d kept fp32, sa = {d, float(sum q) * d} and raw
+// blocks {float d; float s; int8 qs[32]} (40 bytes)
+typedef Q80Args Q81Args;
+// The minimum term of GGUF Q4_1 / Q5_1 (woq_gguf.hip): out[m][n] = epi(out[m][n] + sum_b S[m][b] * mins[n][b]), S the
+// block sums of the activations (S null: woq_min_term_kernel sums A itself).  g carries the epilogue operands and the
+// output (g.w.out / ldo / n / bias, g.epi, g.res, g.aux) for gemm_epilogue4; mins null = the epilogue alone.
+struct MinTermArgs {
+  const void* A;
+  int lda, M, K;
+  int a_vec;            // the rows of A are 16-byte aligned: the block sums may use vector loads (set by the launcher)
+  const float* S;       // [M] rows of K/32 sums: S[m * s_ld + b * s_st]
+  int s_ld, s_st;
+  const uint16_t* mins; // fp16, scale_row() order
+  const uint16_t* scales;  // fp16 block scales d, same order: with qbias != 0 the term is S (mins + qbias d)^T, the two
+  float qbias;             //   products accumulated one after the other (qbias d is exact in fp32, mins + qbias d is not)
+  int ns, ng, kmajor;
+  GemmArgs g;
+};
+constexpr int kMinTermSmallM = 16;          // woq_min_term_kernel: rows it takes ...
+constexpr size_t kMinTermSmallLds = 65536;  // ... while M * K/32 floats fit this much LDS
 hipError_t launch_q4_0_repack(const uint8_t* src, int n, int k, const DeviceWeight& w, hipStream_t stream);
+// type: the GGUF type (3 Q4_1, 6 Q5_0, 7 Q5_1, 8 Q8_0); src: n rows of k/32 blocks on the device
+hipError_t launch_gguf_repack(int type, const uint8_t* src, int n, int k, const DeviceWeight& w, hipStream_t stream);
+hipError_t launch_q8_1_quant(const Q81Args& a, int act_t, hipStream_t stream);
+// block sums of the activation rows into S[m * ng + b] (the pre-pass of launch_min_term_tiled)
+hipError_t launch_block_sums(const void* A, int act_t, int lda, int M, int K, float* S, hipStream_t stream);
+hipError_t launch_min_term(const MinTermArgs& a, int act_t, hipStream_t stream);        // M <= kMinTermSmallM
+hipError_t launch_min_term_tiled(const MinTermArgs& a, hipStream_t stream);            // any M, S given
 hipError_t launch_q8_0_quant(const Q80Args& a, int act_t, hipStream_t stream);
 hipError_t launch_quant_u8(const QuantU8Args& a, int act_t, hipStream_t stream);
 hipError_t launch_i8(const I8Args& a, int bits, hipStream_t stream);

@@ -18,6 +18,10 @@
 //   zps    : same order as scales, int8 (asym only)
 //   shuffle: [K] int32 act-order LUT (GPTQ desc_act), applied as a gather on the A operand
 //   reduce : [ngroups][ns*16] bf16, integer-core blobs only (the int8-compute mode's zero-point correction)
+//   mins   : same order as scales, fp16: the per-block minimum of GGUF Q4_1 / Q5_1 (w = q d + m).  No forward kernel
+//            reads it: woq_min_term_kernel (woq_gguf.hip) adds X's block sums times the mins after the main kernel.
+//            Q4_1's q in 0..15 does not fit the symmetric nibble (q + 8): the nibble holds q, the kernels decode q - 8,
+//            and the min-term pass adds the block sums times 8 d as well (DeviceWeight::min_bias)
 #pragma once
 #include <cstdint>
 
@@ -56,9 +60,13 @@ struct DeviceWeight {
   int32_t f4kind;     // NFloat weight: 0 F4_BNB, 1 F4_E2M1, 2 F4_NF4 (codes in the int4 layout, LUT dequant),
                       // 3 F8_E4M3, 4 F8_E5M2 (raw codes in the int8 layout); -1 = integer
   int32_t compute;    // per-weight arithmetic (nad_device_set_compute): 0 follow the thread / process mode, 1 fp,
-                      // 2 int8 (integer-core blobs and Q4_0 only)
+                      // 2 int8 (integer-core blobs and the GGUF block types only)
   int32_t fold_ok;    // every (q - zp) * scale of the weight is 0 or an fp16 normal: the prefill GEMMs may fold the
                       // group scale into the fp16 B fragment (checked at load)
+  void* mins;         // fp16 block mins of GGUF Q4_1 / Q5_1 (nullptr: the weight has none); the GGUF type itself is
+                      // tagged in src_core_id (capi.hip kGguf*)
+  int32_t min_bias;   // with mins: the layout decodes q - min_bias (8 for Q4_1, whose q in 0..15 is stored as the
+                      // nibble itself; 0 for Q5_1), so w = decoded * d + (min_bias * d + m) -- both products exact
 };
 
 // Tile (s, t) and scale row (s, g) positions.  K-major interleaves the stripes at every K position, so the waves of a
