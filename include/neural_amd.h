@@ -174,7 +174,8 @@ int nad_device_forward(const void* act, int act_dtype, const void* devstor, floa
  * NAD_SCALE_*, m rows of act_dtype): the whole host side of the call -- validation, kernel choice, geometry,
  * workspace sizing -- with every launch recorded instead of issued; no device memory is touched and no GPU is needed.
  * out (versioned by nout): [kernel NAD_KERNEL_*, grid, threads per workgroup, split-K runs, flags (bit 0: scale folded
- * into the fp16 weights; bit 1: gemm4 waves split over K), launches including pre-passes].  Returns the number of values
+ * into the fp16 weights; bit 1: gemm4 waves split over K; bit 2: the M = 1 decode launch takes the specialised
+ * woq_gemv_m1s_kernel, see NAD_GEMV_M1_SPEC), launches including pre-passes].  Returns the number of values
  * written or -1. */
 #define NAD_KERNEL_GEMV_M1 1   /* woq_gemv_m1_kernel: M = 1 decode */
 #define NAD_KERNEL_GEMV 2      /* woq_gemv_kernel: the stripe-stream GEMV, M <= 16 */

@@ -52,7 +52,7 @@ static int env_int(const char* name, int def) {
 // Tuning / A-B switches.  Read from the environment ONCE (at the first forward, or by nad_reload_knobs), never per
 // launch: the eager path an NE graph takes (one bestla_device_f32f32_forward per node) must not scan the environment.
 struct Knobs {
-  int gemv_grid, gemv_waves, gemv_lean, gemv_spw, gemv_disable, gemv_dual, gemv_nst;
+  int gemv_grid, gemv_waves, gemv_lean, gemv_spw, gemv_disable, gemv_dual, gemv_nst, gemv_m1_spec;
   int compute_int8;
   int gemm2_disable, gemm4_all, gemm4_disable, ffn_f32, gemm_kernel, gemm7_bm, splitk_disable;
   int gemm3_stagger, gemm4_fold_all, gemm4_fold, gemm4_ksw;
@@ -65,6 +65,9 @@ static Knobs read_knobs() {
   k.gemv_waves = env_int("NAD_GEMV_WAVES", 0);  // tests / tuning: waves of a stripe-stream launch
   k.gemv_nst = env_int("NAD_GEMV_NST", 0);  // register stages per wave: 0 auto; 1 or 2 (M = 1 kernel), 1 or 3 (M <= 16)
   k.gemv_lean = env_int("NAD_GEMV_LEAN", 1);
+  // M = 1 launches on woq_gemv_m1s_kernel (compact arguments, weight count / reduce / epilogue at compile time) where
+  // one is instantiated; 0: every launch on woq_gemv_m1_kernel with the full GemvArgs (A/B, bit-identity tests)
+  k.gemv_m1_spec = env_int("NAD_GEMV_M1_SPEC", 1);
   k.gemv_dual = env_int("NAD_GEMV_DUAL", 1);  // decode QKV of two formats (int2 Q, K + int4 V) as one launch
   k.gemv_spw = env_int("NAD_GEMV_SPW", 4);
   k.gemv_disable = env_int("NAD_GEMV_DISABLE", 0);
@@ -487,6 +490,7 @@ static int prepare_gemv(GemvArgs& a, int& waves, int& grid, int& gpt_out, const 
   a.dq_mask = 0x000F000Fu;
   a.dq_magic = 0x64006400u;
   a.m1_nst = kn.gemv_nst;
+  a.m1_spec = kn.gemv_m1_spec;
   a.u_q = a.units / grid;
   a.u_r = a.units % grid;
   a.lean = kn.gemv_lean;
@@ -516,7 +520,8 @@ static int try_gemv(const void* act, int act_t, int lda, int m, int k, int nw, c
                     aux, ld_aux))
     return 0;
   const size_t lds = gemv_lds_layout(a, ws[0]->bits, waves, grid);
-  hipError_t e = planned(gemv_uses_m1(a, ws[0]->bits, waves) ? NAD_KERNEL_GEMV_M1 : NAD_KERNEL_GEMV, grid, waves * 64)
+  hipError_t e = planned(gemv_uses_m1(a, ws[0]->bits, waves) ? NAD_KERNEL_GEMV_M1 : NAD_KERNEL_GEMV, grid, waves * 64, 1,
+                         t_plan && gemv_uses_m1s(a, ws[0]->bits, waves) ? 4 : 0)
                      ? hipSuccess
                      : launch_gemv(a, ws[0]->bits, waves, grid, lds, st);
   if (e != hipSuccess) {
@@ -1536,7 +1541,8 @@ static int forward_one(const void* act, int act_dtype, int lda, int m, int k, co
                        hipStream_t st) {
   const DeviceWeight* w = &wr;
   if (m <= kSkinnyMaxM) {
-    // the mid-M kernel from 12 rows of fp16 activations / 8 of fp32 / bf16 (NAD_MID_MIN_M); below that, and for the
+    // the mid-M kernel from 9 rows of fp16 activations where its grid fits the CUs in one round, else from 12, and from 8
+    // rows of fp32 / bf16 (run_mid; NAD_MID_MIN_M overrides); below that, and for the
     // fused QKV / FFN entries at any M <= 16, the skinny GEMV.  Its split-K slabs fit nad_device_workspace_size(m, k).
     if (!int8_compute(*w)) {
       const int r = run_mid(act, act_dtype, lda, m, k, *w, out, ldo, epi, bias, bias_ld, res, ld_res, nullptr, 0, st,

@@ -70,7 +70,8 @@ __device__ unsigned long long nad_trace_buf[kTraceSlots][kTraceMaxWg];
 // once per launch, cold in the instruction cache: ~0.4 us per KB).  Measured (profiles/r06_gemv_tail_ab.txt, same
 // box, alternating): O 4.80 -> 4.55 us, decode 946-951 -> 969-972 tok/s; bit-identical sums (same order).  A
 // branch-free first weight stage (the two-armed load_stage makes hipcc wait vmcnt(0) for the activation loads before
-// the first weight load) measured neutral (943-947 tok/s) and was not kept.
+// the first weight load) measured neutral (943-947 tok/s) on this kernel and was not kept here; woq_gemv_m1s_kernel
+// below, which serves the decode token's launches, has no control flow around any stage's loads.
 #ifndef NAD_GEMV_LEAN_TAIL
 #define NAD_GEMV_LEAN_TAIL 1
 #endif
@@ -651,7 +652,7 @@ __device__ __forceinline__ void m1_body(GemvArgs& a, int bid) {
   const int vpu = a.dual ? 2 : 1;
   const int v0 = u0 * vpu, nv = (u1 - u0) * vpu;
   const bool idle = wave >= nsl;
-  float* part = reinterpret_cast<float*>(smem + a.part_off);  // [nv][NW][16]
+  float* part = reinterpret_cast<float*>(smem + a.part_off);  // [nv][16 columns][NW] (NAD_GEMV_LEAN_TAIL), else [nv][NW][16]
 
   // 1) this wave's activation slices (q = wave + j NW), then the first weight stage
   const auto ra = rsrc(a.A, a.K * ESZ);
@@ -901,6 +902,296 @@ __global__ __launch_bounds__(1024) void woq_gemv_m1_dual_kernel(GemvArgs a, Gemv
     m1_body<B2, G2, AT, false, K2, 1, false, NAD_M1_DUAL_NST>(b, int(blockIdx.x) - ga);
 }
 
+// ------------------------------------------------------------------------------------------------ M = 1, specialised
+// The same stream and the same sums as m1_body for the launches a decode token is made of, with the code a launch runs
+// where no memory latency hides it cut down (tools/gemv_path_bytes.py prints it per instantiation):
+//   * GemvM1Args instead of GemvArgs: 128 bytes for one weight, read by one batch of scalar loads, every
+//     per-launch constant worked out by the host;
+//   * NWT, the weights of the launch, at compile time: 1 (no stripe -> weight lookup at all), 3 (fused QKV) or
+//     2 = the {gate, up} pair, which also fixes the epilogue: a plain store for 1 and 3, SiLU(gate) * up for 2.  Every
+//     other epilogue stays on woq_gemv_m1_kernel with its runtime switch;
+//   * L16, whether the launch reduces 16 slots per column (16 waves with a K-slice each), at compile time: one reduce
+//     per instantiation, straight after the stream;
+//   * a stage's loads are never under control flow (past-the-end stages select the out-of-range offset), so nothing
+//     makes hipcc wait for the activation loads before it issues the first weight stage.
+template <int NWT>
+struct M1Sel {  // the wave-uniform (weight, stripe within it) of virtual stripe v
+  int w, s;
+  __device__ __forceinline__ M1Sel(const GemvM1Args<NWT>& a, int v) {
+    if constexpr (NWT == 1) {
+      w = 0;
+      s = v;
+    } else if constexpr (NWT == 2) {
+      w = v & 1;
+      s = v >> 1;
+    } else {
+      w = (v >= a.sb1 ? 1 : 0) + (v >= a.sb2 ? 1 : 0);
+      s = v - (w == 0 ? 0 : (w == 1 ? a.sb1 : a.sb2));
+    }
+  }
+};
+template <int NWT, class T>
+__device__ __forceinline__ T m1_pick(int w, const T (&x)[3]) {
+  if constexpr (NWT == 1) return x[0];
+  else if constexpr (NWT == 2) return w == 0 ? x[0] : x[1];
+  else return sel3(w, x[0], x[1], x[2]);
+}
+#define NAD_M1_FIELD(args, wi, f) \
+  m1_pick<NWT>(wi, {args.w[0].f, args.w[NWT > 1 ? 1 : 0].f, args.w[NWT > 2 ? 2 : 0].f})
+
+template <int NWT, bool ASYM>
+__device__ __forceinline__ void m1s_cursor_stripe(const GemvM1Args<NWT>& a, StageCursor& c, int v, bool on) {
+  const M1Sel<NWT> vs(a, v);
+  c.s = vs.s;
+  const void* const tp[3] = {a.w[0].tiles, a.w[NWT > 1 ? 1 : 0].tiles, a.w[NWT > 2 ? 2 : 0].tiles};
+  const void* const sp[3] = {a.w[0].scales, a.w[NWT > 1 ? 1 : 0].scales, a.w[NWT > 2 ? 2 : 0].scales};
+  const int tb[3] = {a.w[0].tiles_bytes, a.w[NWT > 1 ? 1 : 0].tiles_bytes, a.w[NWT > 2 ? 2 : 0].tiles_bytes};
+  const int sb[3] = {a.w[0].scales_bytes, a.w[NWT > 1 ? 1 : 0].scales_bytes, a.w[NWT > 2 ? 2 : 0].scales_bytes};
+  // off: zero records, every access out of range (idle waves, past-the-end stages)
+  c.rt = rsrc(m1_pick<NWT>(vs.w, tp), on ? m1_pick<NWT>(vs.w, tb) : 0);
+  c.rs = rsrc(m1_pick<NWT>(vs.w, sp), on ? m1_pick<NWT>(vs.w, sb) : 0);
+  if constexpr (ASYM) {
+    const void* const zp[3] = {a.w[0].zps, a.w[NWT > 1 ? 1 : 0].zps, a.w[NWT > 2 ? 2 : 0].zps};
+    const int zb[3] = {a.w[0].zps_bytes, a.w[NWT > 1 ? 1 : 0].zps_bytes, a.w[NWT > 2 ? 2 : 0].zps_bytes};
+    c.rz = rsrc(m1_pick<NWT>(vs.w, zp), on ? m1_pick<NWT>(vs.w, zb) : 0);
+  } else {
+    c.rz = c.rs;
+  }
+}
+
+// load_stage without control flow around the loads: a past-the-end stage (c.j >= nv) issues the same loads at the
+// out-of-range offset -- same vmcnt footprint, no memory touched -- and leaves the cursor alone
+template <int GPT, bool ASYM, int KSN, int NWT>
+__device__ __forceinline__ void m1s_load_stage(const GemvM1Args<NWT>& a, StageRegs<GPT, KSN>& S, StageCursor& c, int nv,
+                                               int nsl, int wave, int NW, int v0, int lane, int vs) {
+  const bool on = c.j < nv;
+  const int nt = a.nt, ng = a.ng;
+  const int t0 = c.q * KSN;
+  const int tb = (c.s * nt + t0) * 1024;
+  const int rowb = a.scale_t == kScaleF32 ? 64 : 32;  // bytes per scale row of 16
+#pragma unroll
+  for (int i = 0; i < KSN; i++) {
+    const bool live = on && t0 + i < nt;
+    S.b[i] = __builtin_bit_cast(u4_t, __builtin_amdgcn_raw_buffer_load_b128(c.rt, (live ? tb + i * 1024 : kOOB) + lane * 16, 0, NAD_TILE_AUX));
+#pragma unroll
+    for (int g = 0; g < GPT; g++) {
+      const int grp = GPT == 1 ? ((t0 + i) >> a.tpg_shift) : (t0 + i) * GPT + g;
+      const bool gl = live && (GPT == 1 || grp < ng);
+      const int row = c.s * ng + grp;
+      S.sc[i][g] = __builtin_amdgcn_raw_buffer_load_b32(c.rs, (gl ? row * rowb : kOOB) + vs, 0, 0);
+      if constexpr (ASYM)
+        S.zp[i][g] = int(int8_t(__builtin_amdgcn_raw_buffer_load_b8(c.rz, (gl ? row * 16 : kOOB) + (lane & 15), 0, 0)));
+      else
+        S.zp[i][g] = 0;
+    }
+  }
+  if (on) {
+    c.q += NW;
+    if (c.q >= nsl) {
+      c.q = wave;
+      c.j++;
+      m1s_cursor_stripe<NWT, ASYM>(a, c, v0 + c.j, c.j < nv);
+    }
+  }
+}
+
+template <int BITS, int GPT, int AT, bool ASYM, int KSN, int SPW, int NST, int ST, int NWT, bool L16>
+__global__ __launch_bounds__((m1_max_threads<GPT, KSN>())) void woq_gemv_m1s_kernel(GemvM1Args<NWT> a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  static_assert(NWT >= 1 && NWT <= 3, "1 weight, the {gate, up} pair, or 3 weights");
+  constexpr int KT = BITS == 4 ? 128 : 256, SPT = KT / 32, SPG = SPT / GPT;
+  constexpr int RB = lean_row_bytes(BITS, KSN);  // one fp16 row of a slice
+  constexpr int UNITS = KSN * KT / 8;             // 8-element staging units per slice
+  constexpr int UPL = UNITS >= 64 ? UNITS / 64 : 1;  // ... per lane (2-tile int4 slices: lanes < 32 hold one)
+  constexpr bool PART = UNITS < 64;
+  constexpr int BIAS = BITS == 4 ? 8 : 2;
+  constexpr int ESZ = AT == kActF32 ? 4 : 2;
+  constexpr bool HL = AT != kActF16;  // fp32 / bf16 rows split into fp16 hi + lo (MFMA rows 0 and 8)
+  constexpr int VPU = NWT == 2 ? 2 : 1;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6));
+  const int NW = L16 ? 16 : a.nw;
+  const int nsl = a.nsl;
+  const bool ulane = !PART || lane < UNITS;  // this lane holds a staging unit of each slice
+  NAD_TRACE(0);
+  const int bid = int(blockIdx.x);
+  const int u0 = bid * a.u_q + min(bid, a.u_r);
+  const int nu = a.u_q + (bid < a.u_r ? 1 : 0);
+  const int v0 = u0 * VPU, nv = nu * VPU;
+  const bool idle = !L16 && wave >= nsl;  // L16: every wave owns a slice
+  float* part = reinterpret_cast<float*>(smem + a.part_off);  // [nv][16 columns][NW]
+
+  // 1) this wave's activation slices (q = wave + j NW; past the end of K the buffer returns zeros), then the first
+  //    weight stage
+  const auto ra = rsrc(a.A, a.a_bytes);
+  uint4 x[SPW * UPL][2];
+#pragma unroll
+  for (int j = 0; j < SPW * UPL; j++) {
+    const int q = wave + (j / UPL) * NW, k = q * (KSN * KT) + ((j % UPL) * 64 + lane) * 8;
+    const int off = ulane ? k * ESZ : kOOB;
+    x[j][0] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(ra, off, 0, 0));
+    if constexpr (ESZ == 4) x[j][1] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(ra, off + 16, 0, 0));
+  }
+  const int vs = a.scale_t == kScaleF32 ? (lane & 15) * 4 : (lane & 14) * 2;
+  StageCursor lc;
+  lc.j = idle ? nv : 0;
+  lc.q = wave;
+  m1s_cursor_stripe<NWT, ASYM>(a, lc, v0, lc.j < nv);
+  StageRegs<GPT, KSN> S[NST];
+  m1s_load_stage<GPT, ASYM, KSN, NWT>(a, S[0], lc, nv, nsl, wave, NW, v0, lane, vs);
+  NAD_TRACE(4);
+
+  // 2) stage the slices into this wave's rows (LDS ops of one wave complete in order: no barrier)
+  char* wrow = smem + wave * lean_wave_lds(BITS, KSN, SPW);
+#pragma unroll
+  for (int u = 0; u < UPL; u++)
+    if (ulane) *reinterpret_cast<uint4*>(wrow + (u * 64 + lane) * 16) = make_uint4(0u, 0u, 0u, 0u);
+#pragma unroll
+  for (int j = 0; j < SPW * UPL; j++) {
+    if (!ulane) break;
+    h8_t hi, lo;
+    if constexpr (AT == kActF16) {
+      hi = __builtin_bit_cast(h8_t, x[j][0]);
+    } else {
+      float f[8];
+      unit_to_f32(AT, x[j][0], x[j][1], f);
+#pragma unroll
+      for (int e = 0; e < 8; e++) {
+        hi[e] = _Float16(f[e]);
+        lo[e] = _Float16(f[e] - float(hi[e]));
+      }
+    }
+    char* row = wrow + RB + (j / UPL) * 2 * RB + ((j % UPL) * 64 + lane) * 16;
+    *reinterpret_cast<h8_t*>(row) = hi;
+    if constexpr (HL) *reinterpret_cast<h8_t*>(row + RB) = lo;
+  }
+#pragma unroll
+  for (int i = 1; i < NST; i++) m1s_load_stage<GPT, ASYM, KSN, NWT>(a, S[i], lc, nv, nsl, wave, NW, v0, lane, vs);
+  NAD_TRACE(1);
+
+  // 3) the stream: MFMA row 0 = hi (lane m 0), row 8 = lo (lane m 8), every other row reads the zero row
+  const int m = lane & 15, kq = lane >> 4;
+  const bool isrow = m == 0 || (HL && m == 8);
+  const char* abase = wrow + (isrow ? (m == 0 ? RB : 2 * RB) : 0) + kq * 16;
+  const int slice_step = isrow ? 2 * RB : 0;
+  const int ssh = a.scale_t == kScaleF32 ? 0 : (lane & 1) * 16;
+  Dq4 dq;
+  dq.m0 = __builtin_amdgcn_readfirstlane(a.dq_mask);
+  dq.m1 = dq.m0 << 4;
+  dq.mag = __builtin_amdgcn_readfirstlane(a.dq_magic);
+  dq.s16 = splat(1.f / 16.f);
+  const h2_t zc0 = splat(-(1024.f + BIAS)), zc1 = splat(-(64.f + BIAS));
+
+  f4_t acc = {0.f, 0.f, 0.f, 0.f};
+  int cj = idle ? nv : 0, cq = wave, cs = 0;  // compute cursor: local stripe, K-slice, slice ordinal of this wave
+
+  auto compute_stage = [&](const StageRegs<GPT, KSN>& S) {
+    if (cj >= nv) return;
+    const char* ab = abase + cs * slice_step;
+    f4_t accg[KSN];
+#pragma unroll
+    for (int d = 0; d < SPT; d++) {
+      const int g = GPT == 1 ? 0 : d / SPG;
+#pragma unroll
+      for (int i = 0; i < KSN; i++) {
+        h8_t bf;
+        if constexpr (BITS == 4) {
+          if constexpr (ASYM) {
+            const float z = float(S.zp[i][g]);
+            bf = dequant4(S.b[i][d], dq, zc0 - splat(z), zc1 - splat(z));
+          } else {
+            bf = dequant4(S.b[i][d], dq, zc0, zc1);
+          }
+        } else {
+          bf = BITS == 2 ? dequant2_step(S.b[i], d, BIAS + S.zp[i][g])
+                         : dequant_step<BITS>(S.b[i], d, zp_const(BIAS + S.zp[i][g]));
+        }
+        const h8_t af = *reinterpret_cast<const h8_t*>(ab + i * KT * 2 + d * 64);
+        accg[i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af, bf, d % SPG == 0 ? f4_t{0.f, 0.f, 0.f, 0.f} : accg[i],
+                                                         0, 0, 0);
+      }
+      if ((d + 1) % SPG == 0) {  // group end: scale each tile's group partial into the stripe sum, in tile order
+#pragma unroll
+        for (int i = 0; i < KSN; i++) acc += accg[i] * scale_to_f32<ST>(S.sc[i][g], a.scale_t, ssh);
+      }
+    }
+    cq += NW;
+    cs++;
+    if (cq >= nsl) {  // this wave's last slice of stripe cj: publish its partial (row 0 + row 8 = hi + lo)
+      float r = acc[0];
+      if constexpr (HL) {
+        r += __shfl_down(r, 32, 64);
+      }
+      if (lane < 16) part[(size_t(cj) * 16 + lane) * NW + wave] = r;  // a column's slots together
+      acc = f4_t{0.f, 0.f, 0.f, 0.f};
+      cq = wave;
+      cs = 0;
+      cj++;
+    }
+  };
+
+  while (cj < nv) {
+#pragma unroll
+    for (int i = 0; i < NST; i++) {
+      compute_stage(S[i]);
+      m1s_load_stage<GPT, ASYM, KSN, NWT>(a, S[i], lc, nv, nsl, wave, NW, v0, lane, vs);
+    }
+  }
+  NAD_TRACE_MAX(2);
+  __syncthreads();
+
+  // 4) sum each stripe's wave slots in wave order (m1_body's order exactly), then the store
+  const int nout = nu * 16;
+  for (int o = threadIdx.x; o < nout; o += NW * 64) {
+    const int p = o >> 4, nn = o & 15;
+    float y[VPU];
+#pragma unroll
+    for (int h = 0; h < VPU; h++) {
+      if constexpr (L16) {  // four 16-B reads per column, no clamps or masks
+        const float4* ps = reinterpret_cast<const float4*>(part + (size_t(p * VPU + h) * 16 + nn) * 16);
+        const float4 t0 = ps[0], t1 = ps[1], t2 = ps[2], t3 = ps[3];
+        // s_i sums slots i, i + 4, i + 8, i + 12
+        const float s0 = ((t0.x + t1.x) + t2.x) + t3.x, s1 = ((t0.y + t1.y) + t2.y) + t3.y;
+        const float s2 = ((t0.z + t1.z) + t2.z) + t3.z, s3 = ((t0.w + t1.w) + t2.w) + t3.w;
+        y[h] = (s0 + s1) + (s2 + s3);
+      } else {  // all slots read at once (one LDS round trip)
+        const int nwl = min(NW, nsl);
+        const float* ps = part + (size_t(p * VPU + h) * 16 + nn) * NW;
+        float t[16];
+#pragma unroll
+        for (int w = 0; w < 16; w++) t[w] = ps[min(w, nwl - 1)];
+        const int full = nwl & ~3;
+        float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+#pragma unroll
+        for (int w = 0; w < 16; w += 4)
+          if (w < full) {
+            s0 += t[w];
+            s1 += t[w + 1];
+            s2 += t[w + 2];
+            s3 += t[w + 3];
+          }
+#pragma unroll
+        for (int w = 0; w < 16; w++)
+          if (w >= full && w < nwl) s0 += t[w];
+        y[h] = (s0 + s1) + (s2 + s3);
+      }
+    }
+    const M1Sel<NWT> vsel(a, v0 + p * VPU);
+    const int wsel = NWT == 2 ? 0 : vsel.w;
+    const int n = vsel.s * 16 + nn;
+    if (n >= NAD_M1_FIELD(a, wsel, n)) continue;
+    float* out = NAD_M1_FIELD(a, wsel, out);
+    if constexpr (NWT == 2) {  // SiLU(gate) * up
+      const float t1 = silu_f(y[0]);
+      if (a.aux) a.aux[n] = t1;
+      out[n] = t1 * y[VPU - 1];
+    } else {
+      out[n] = y[0];
+    }
+  }
+  NAD_TRACE(3);
+}
+
 // ------------------------------------------------------------------------------------------------ launcher
 template <int BITS, int HILO, int GPT, bool ASYM, int NST>
 static hipError_t gemv_launch5(const GemvArgs& a, dim3 g, dim3 b, size_t lds, hipStream_t st) {
@@ -979,6 +1270,151 @@ static hipError_t gemv_m1_launch4(const GemvArgs& a, dim3 g, dim3 b, size_t lds,
                            : gemv_m1_launch5<BITS, GPT, AT, ASYM, KS, 2, ST>(a, g, b, lds, st);
   }
 }
+// woq_gemv_m1s_kernel.  Its instantiations are their own objects (GEMV_PART=2: int4, GEMV_PART=3: int2) next to
+// the general ones; gemv_m1s_launch_b{4,2} return false where no instantiation serves the launch -- any epilogue
+// but {none, SiLU*mul}, two weights, a batch, and the geometries left out below -- and woq_gemv_m1_kernel takes it.
+// e == nullptr: a dry run, nothing is launched.
+template <int NWT>
+static GemvM1Args<NWT> m1s_args(const GemvArgs& a, int ksn, int waves) {
+  GemvM1Args<NWT> c{};
+  const int esz = a.act_t == kActF32 ? 4 : 2, ssz = a.scale_t == kScaleF32 ? 4 : 2;
+  c.A = a.A;
+  c.a_bytes = a.K * esz;
+  c.nsl = (a.nt + ksn - 1) / ksn;
+  c.u_q = a.u_q;
+  c.u_r = a.u_r;
+  c.nt = a.nt;
+  c.ng = a.ng;
+  c.tpg_shift = a.tpg_shift;
+  c.scale_t = a.scale_t;
+  c.nw = waves;
+  c.part_off = a.part_off;
+  c.dq_mask = a.dq_mask;
+  c.dq_magic = a.dq_magic;
+  c.sb1 = a.stripe_base[1];
+  c.sb2 = a.stripe_base[2];
+  for (int i = 0; i < NWT; i++) {
+    const SkinnyWeight& w = a.w[i];
+    c.w[i].tiles = w.tiles;
+    c.w[i].scales = w.scales;
+    c.w[i].zps = w.zps;
+    c.w[i].tiles_bytes = w.ns * a.nt * 1024;
+    c.w[i].scales_bytes = w.ns * a.ng * 16 * ssz;
+    c.w[i].zps_bytes = w.ns * a.ng * 16;
+    c.w[i].n = w.n;
+    c.w[i].out = w.out;
+  }
+  c.aux = a.aux;
+  return c;
+}
+template <int BITS, int GPT, int AT, bool ASYM, int KSN, int SPW, int NST, int ST, int NWT, bool L16>
+static hipError_t m1s_go(const GemvArgs& a, dim3 g, dim3 b, size_t lds, hipStream_t st) {
+  auto k = woq_gemv_m1s_kernel<BITS, GPT, AT, ASYM, KSN, SPW, NST, ST, NWT, L16>;
+  static bool attr_set = false;
+  if (!attr_set) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       160 * 1024);
+    if (e != hipSuccess) return e;
+    attr_set = true;
+  }
+  const GemvM1Args<NWT> c = m1s_args<NWT>(a, KSN, int(b.x / 64));
+  hipLaunchKernelGGL(k, g, b, lds, st, c);
+  return hipGetLastError();
+}
+// weights of the launch as woq_gemv_m1s_kernel's NWT (0: not served)
+static int m1s_nwt(const GemvArgs& a) {
+  if (a.batch || !a.m1_spec) return 0;
+  if (a.dual) return a.epi == kEpiSiluMul ? 2 : 0;
+  if (a.epi != kEpiNone) return 0;
+  const int nw = 1 + (a.stripe_base[1] != INT_MAX ? 1 : 0) + (a.stripe_base[2] != INT_MAX ? 1 : 0);
+  return nw == 1 || nw == 3 ? nw : 0;
+}
+// Instantiated: slices of 1 or 2 tiles, one per wave: every weight count, both reduces, two register stages
+// for one weight only (lm_head); 4-tile slices with fewer than 16 slots per column: two per wave for every weight count
+// (two stages: one weight), four per wave for one weight (the long K of a down projection).
+template <int BITS, int GPT, int AT, bool ASYM, int ST>
+static bool m1s_launch3(const GemvArgs& a, dim3 g, dim3 b, size_t lds, hipStream_t st, hipError_t* e) {
+  const int nwt = m1s_nwt(a), waves = int(b.x / 64), ks = lean_ks(a);
+  if (nwt == 0) return false;
+  const int nsl = (a.nt + ks - 1) / ks;
+  const bool l16 = waves == 16 && nsl >= 16;
+  const int spw = m1_stages_per_wave(a, ks, waves);
+  const int nst = a.m1_nst == 1 || a.m1_nst == 2 ? a.m1_nst : (spw >= 7 || (ks == 1 && spw >= 4) ? 2 : 1);
+#define NAD_M1S(KSN, SPW, NST, NWT, L16)                                                         \
+  do {                                                                                           \
+    if (e) *e = m1s_go<BITS, GPT, AT, ASYM, KSN, SPW, NST, ST, NWT, L16>(a, g, b, lds, st);      \
+    return true;                                                                                 \
+  } while (0)
+#define NAD_M1S_NARROW(KSN)                               \
+  do {                                                    \
+    if (nst == 1) {                                       \
+      if (nwt == 1 && l16) NAD_M1S(KSN, 1, 1, 1, true);   \
+      if (nwt == 1) NAD_M1S(KSN, 1, 1, 1, false);         \
+      if (nwt == 2 && l16) NAD_M1S(KSN, 1, 1, 2, true);   \
+      if (nwt == 2) NAD_M1S(KSN, 1, 1, 2, false);         \
+      if (nwt == 3 && l16) NAD_M1S(KSN, 1, 1, 3, true);   \
+      if (nwt == 3) NAD_M1S(KSN, 1, 1, 3, false);         \
+    } else if (nwt == 1) {                                \
+      if (l16) NAD_M1S(KSN, 1, 2, 1, true);               \
+      NAD_M1S(KSN, 1, 2, 1, false);                       \
+    }                                                     \
+    return false;                                         \
+  } while (0)
+  if (ks == 1) NAD_M1S_NARROW(1);
+  if (ks == 2) NAD_M1S_NARROW(2);
+  if (l16 || (GPT != 1 && waves > 8)) return false;
+  if (lean_spw(a) == 4) {
+    if (nwt == 1 && nst == 1) NAD_M1S(KS, 4, 1, 1, false);
+    return false;
+  }
+  if (nst == 1) {
+    if (nwt == 1) NAD_M1S(KS, 2, 1, 1, false);
+    if (nwt == 2) NAD_M1S(KS, 2, 1, 2, false);
+    NAD_M1S(KS, 2, 1, 3, false);
+  }
+  if (nwt == 1) NAD_M1S(KS, 2, 2, 1, false);
+  return false;
+#undef NAD_M1S_NARROW
+#undef NAD_M1S
+}
+#if !defined(GEMV_PART) || GEMV_PART == 2
+// int4: every activation type at one group per tile, fp32 activations at two
+bool gemv_m1s_launch_b4(const GemvArgs& a, int gpt, dim3 g, dim3 b, size_t lds, hipStream_t st, hipError_t* e) {
+  if (gpt == 1) {
+    if (a.act_t == kActF32) return a.asym ? m1s_launch3<4, 1, kActF32, true, -1>(a, g, b, lds, st, e)
+                                          : m1s_launch3<4, 1, kActF32, false, -1>(a, g, b, lds, st, e);
+    if (a.act_t == kActF16) return a.asym ? m1s_launch3<4, 1, kActF16, true, -1>(a, g, b, lds, st, e)
+                                          : m1s_launch3<4, 1, kActF16, false, -1>(a, g, b, lds, st, e);
+    return a.asym ? m1s_launch3<4, 1, kActBF16, true, -1>(a, g, b, lds, st, e)
+                  : m1s_launch3<4, 1, kActBF16, false, -1>(a, g, b, lds, st, e);
+  }
+  if (gpt == 2 && a.act_t == kActF32)
+    return a.asym ? m1s_launch3<4, 2, kActF32, true, -1>(a, g, b, lds, st, e)
+                  : m1s_launch3<4, 2, kActF32, false, -1>(a, g, b, lds, st, e);
+  return false;
+}
+#else
+bool gemv_m1s_launch_b4(const GemvArgs& a, int gpt, dim3 g, dim3 b, size_t lds, hipStream_t st, hipError_t* e);
+#endif
+#if !defined(GEMV_PART) || GEMV_PART == 3
+// int2: symmetric weights with fp32 activations, each scale type (as woq_gemv_m1_kernel's int2 instantiations)
+template <int GPT>
+static bool m1s_launch_b2g(const GemvArgs& a, dim3 g, dim3 b, size_t lds, hipStream_t st, hipError_t* e) {
+  if (a.scale_t == kScaleF32) return m1s_launch3<2, GPT, kActF32, false, NAD_INT2_ST ? kScaleF32 : -1>(a, g, b, lds, st, e);
+  if (a.scale_t == kScaleBF16) return m1s_launch3<2, GPT, kActF32, false, NAD_INT2_ST ? kScaleBF16 : -1>(a, g, b, lds, st, e);
+  return m1s_launch3<2, GPT, kActF32, false, NAD_INT2_ST ? kScaleF16 : -1>(a, g, b, lds, st, e);
+}
+bool gemv_m1s_launch_b2(const GemvArgs& a, int gpt, dim3 g, dim3 b, size_t lds, hipStream_t st, hipError_t* e) {
+  if (a.asym || a.act_t != kActF32) return false;
+  if (gpt == 1) return m1s_launch_b2g<1>(a, g, b, lds, st, e);
+  if (gpt == 2) return m1s_launch_b2g<2>(a, g, b, lds, st, e);
+  if (gpt == 4) return m1s_launch_b2g<4>(a, g, b, lds, st, e);
+  return false;
+}
+#else
+bool gemv_m1s_launch_b2(const GemvArgs& a, int gpt, dim3 g, dim3 b, size_t lds, hipStream_t st, hipError_t* e);
+#endif
+
 template <int BITS, int GPT>
 static hipError_t gemv_m1_launch2(const GemvArgs& a, dim3 g, dim3 b, size_t lds, hipStream_t st) {
   if (a.act_t == kActF32) return a.asym ? gemv_m1_launch4<BITS, GPT, kActF32, true>(a, g, b, lds, st)
@@ -1039,7 +1475,7 @@ static hipError_t gemv_launch1(const GemvArgs& a, int hilo, int gpt, dim3 g, dim
 
 // LDS layout (and its size) of one launch: activation rows, then the partial-sum slots [nv][waves][M][16]
 size_t gemv_lds_layout(GemvArgs& a, int bits, int waves, int grid) {
-  if (lean_ok(a, bits, waves)) {  // woq_gemv_m1_kernel: per-wave rows, then the partial slots [nv][waves][16]
+  if (lean_ok(a, bits, waves)) {  // the M = 1 kernels: per-wave rows, then the partial slots [nv][16 columns][waves]
     const int upw = (a.units + grid - 1) / grid;
     a.part_off = waves * lean_wave_lds(bits, lean_ks(a), lean_spw(a));
     return size_t(a.part_off) + size_t(upw) * (a.dual ? 2 : 1) * waves * 16 * 4;
@@ -1110,6 +1546,14 @@ int gemv_groups_per_tile(int bits, int nt, int ng, int bs, int* tpg) {
 
 bool gemv_uses_m1(const GemvArgs& a, int bits, int waves) { return lean_ok(a, bits, waves); }
 
+bool gemv_uses_m1s(const GemvArgs& a, int bits, int waves) {
+  int tpg = 0;
+  const int gpt = gemv_groups_per_tile(bits, a.nt, a.ng, a.bs, &tpg);
+  if (!lean_ok(a, bits, waves)) return false;
+  return bits == 4 ? gemv_m1s_launch_b4(a, gpt, dim3(1), dim3(waves * 64), 0, nullptr, nullptr)
+                   : gemv_m1s_launch_b2(a, gpt, dim3(1), dim3(waves * 64), 0, nullptr, nullptr);
+}
+
 bool gemv_dual_ok(const GemvArgs& a, int bits_a, const GemvArgs& b, int bits_b, int waves) {
   int tpg = 0;
   const int ga = gemv_groups_per_tile(bits_a, a.nt, a.ng, a.bs, &tpg), gb = gemv_groups_per_tile(bits_b, b.nt, b.ng, b.bs, &tpg);
@@ -1150,7 +1594,12 @@ hipError_t launch_gemv(const GemvArgs& a, int bits, int waves, int grid, size_t 
   const int gpt = gemv_groups_per_tile(bits, a.nt, a.ng, a.bs, &tpg);
   if (gpt == 0) return hipErrorInvalidValue;
   dim3 g(grid), b(waves * 64);
-  if (lean_ok(a, bits, waves)) return gemv_m1_launch(a, bits, gpt, g, b, lds, stream);
+  if (lean_ok(a, bits, waves)) {
+    hipError_t e = hipSuccess;
+    if (bits == 4 ? gemv_m1s_launch_b4(a, gpt, g, b, lds, stream, &e) : gemv_m1s_launch_b2(a, gpt, g, b, lds, stream, &e))
+      return e;
+    return gemv_m1_launch(a, bits, gpt, g, b, lds, stream);
+  }
   if (bits == 4) return gemv_launch1<4>(a, hilo, gpt, g, b, lds, stream);
   if (bits == 2) return gemv_launch1<2>(a, hilo, gpt, g, b, lds, stream);
   return gemv_launch1<8>(a, hilo, gpt, g, b, lds, stream);

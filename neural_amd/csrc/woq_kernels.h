@@ -147,6 +147,36 @@ struct GemvArgs {
   const GemvBatchEnt* batch;  // batched M = 1 launch (woq_gemv_m1_kernel<..., BATCH>): problem p = blockIdx / batch_wpp
   int batch_wpp;              //   reads its activations / weight / output from batch[p]; u_q / u_r split one problem
   int m1_nst;                 // woq_gemv_m1_kernel: register stages in flight per wave (0 = by the stages per wave)
+  int m1_spec;                // M = 1 launches may take woq_gemv_m1s_kernel (NAD_GEMV_M1_SPEC; 0: always the kernel above)
+};
+
+// The argument block of woq_gemv_m1s_kernel: only what that kernel reads, in the order it reads it, with everything
+// that is constant per launch worked out by launch_gemv (buffer sizes, K-slices per stripe, units per workgroup).  A
+// one-weight launch is 128 bytes -- two scalar-cache lines, fetched by one batch of scalar loads -- where GemvArgs is
+// 480.  NWS: weights in the launch (1; 3 = fused QKV; 2 = the {gate, up} pair of the SiLU*mul epilogue).
+struct GemvM1Weight {
+  const void* tiles;
+  const void* scales;
+  const int8_t* zps;
+  int tiles_bytes, scales_bytes, zps_bytes;  // buffer-resource sizes: ns * nt * 1024, ns * ng * 16 * scale size, ns * ng * 16
+  int n;                                     // output columns (tail)
+  float* out;                                // (tail)
+};
+template <int NWS>
+struct GemvM1Args {
+  const void* A;
+  int a_bytes;          // K * element size
+  int nsl;              // K-slices per stripe
+  int u_q, u_r;         // units per workgroup: u_q, one more for the first u_r workgroups
+  int nt, ng;
+  int tpg_shift;        // one group per tile or coarser: log2(tiles per group)
+  int scale_t;
+  int nw;               // waves per workgroup
+  int part_off;         // LDS byte offset of the partial-sum slots
+  uint32_t dq_mask, dq_magic;
+  int sb1, sb2;         // NWS == 3: first virtual stripe of weights 1 and 2
+  GemvM1Weight w[NWS];
+  float* aux;           // NWS == 2: optional silu(gate) output (tail)
 };
 
 hipError_t launch_repack(const RepackArgs& a, hipStream_t stream);
@@ -259,6 +289,8 @@ void gemv_lean_slices(GemvArgs& a, int bits, int* waves, int ks_pref);
 hipError_t launch_gemv(const GemvArgs& a, int bits, int waves, int grid, size_t lds, hipStream_t stream);
 // whether launch_gemv would take woq_gemv_m1_kernel for these arguments
 bool gemv_uses_m1(const GemvArgs& a, int bits, int waves);
+// ... and would serve it with woq_gemv_m1s_kernel (a.m1_spec, and an instantiation for the launch exists)
+bool gemv_uses_m1s(const GemvArgs& a, int bits, int waves);
 // two M = 1 launches of different formats as one (int2 a + int4 b at groups of 64 or 128, fp32 activations, sym,
 // 16 waves each; a on workgroups [0, ga), b on [ga, ga + gb))
 bool gemv_dual_ok(const GemvArgs& a, int bits_a, const GemvArgs& b, int bits_b, int waves);
