@@ -1,0 +1,152 @@
+// capi_internal.h -- what the units behind the extern "C" boundary share: capi.hip (errors, knobs, dry runs, device
+// context, workspace, compute mode), capi_load.hip, capi_forward.hip, capi_host.hip.  Nothing here is exported.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <string>
+
+#include "../../include/neural_amd.h"
+#include "btla_format.h"
+#include "woq_kernels.h"
+
+#pragma GCC visibility push(hidden)
+
+// ------------------------------------------------------------------------------------------------ errors (capi.hip)
+void set_err(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
+void report(const char* where);
+#define HIP_OK(expr)                                                           \
+  do {                                                                         \
+    hipError_t e_ = (expr);                                                    \
+    if (e_ != hipSuccess) {                                                    \
+      set_err("%s failed: %s", #expr, hipGetErrorString(e_));                  \
+      return -1;                                                               \
+    }                                                                          \
+  } while (0)
+
+// ------------------------------------------------------------------------------------------------ knobs (capi.hip)
+// Tuning / A-B switches.  Read from the environment ONCE (at the first forward, or by nad_reload_knobs), never per
+// launch: the eager path an NE graph takes (one bestla_device_f32f32_forward per node) must not scan the environment.
+struct Knobs {
+  int gemv_grid, gemv_waves, gemv_lean, gemv_spw, gemv_disable, gemv_dual, gemv_nst, gemv_m1_spec;
+  int compute_int8;
+  int gemm2_disable, gemm4_all, gemm4_disable, ffn_f32, gemm_kernel, gemm7_bm, splitk_disable;
+  int gemm3_stagger, gemm4_fold_all, gemm4_fold, gemm4_ksw;
+  int mid_min_m, mid_max_m, mid_ks, mid_xcd, mid_wide, gemm_xcd, gemm7_model, gemm7_fuse;
+  int host_cache_mb;
+};
+const Knobs& knobs();
+
+// ------------------------------------------------------------------------------------------------ dry runs (capi.hip)
+// nad_plan_forward runs the whole host side of a forward (validation, kernel choice, geometry, workspace sizing) with
+// every launch replaced by a record of it: which kernel would serve the call, and what the host path costs per call.
+struct NadPlan {
+  int kernel = 0, grid = 0, block = 0, ksplit = 1, fold = 0, launches = 0;
+};
+void set_plan(NadPlan* p);  // the calling thread's forwards record into *p until set_plan(nullptr)
+bool planning();
+// true (and the launch recorded) in a dry run; main = false for pre-passes (conversions, activation quantizers)
+bool planned(int kernel, int grid, int block, int ksplit = 1, int fold = 0, bool main = true);
+inline bool planned_pass() { return planned(0, 0, 0, 1, 0, false); }
+
+// One launch: recorded in a dry run (`recorded`, the result of planned()), else issued by fn; false, with the error
+// "<what> launch failed: ..." set, when it fails.
+template <class F>
+static inline bool launch(bool recorded, const char* what, F&& fn) {
+  if (recorded) return true;
+  const hipError_t e = fn();
+  if (e == hipSuccess) return true;
+  set_err("%s launch failed: %s", what, hipGetErrorString(e));
+  return false;
+}
+
+// ------------------------------------------------------------------------------------------------ device context
+struct NadDevice {
+  int device;
+  hipStream_t stream;
+  bool profile;
+};
+
+const nad::DeviceWeight* as_weight(const void* p);  // null, with the error set, for anything but a loaded weight
+
+// ------------------------------------------------------------------------------------------------ workspace (capi.hip)
+void* workspace_for(size_t bytes, hipStream_t st);
+struct CallWorkspace {  // RAII binding of a reference call's workspace argument
+  CallWorkspace(void* p, size_t b);
+  ~CallWorkspace();
+};
+
+// ------------------------------------------------------------------------------------------------ compute mode (capi.hip)
+// a GGUF Q4_0 matrix (nad_q4_0_device_load) carries this in src_core_id: its int8 arithmetic is Q8_0 x Q4_0
+constexpr uint64_t kGgufQ4_0 = 0x3054344655474700ull;  // "\0GGUF4Q0"
+// the other GGUF block types (nad_gguf_device_load): the same tag with the type's two characters
+constexpr uint64_t kGgufQ4_1 = 0x3154344655474700ull;  // "\0GGUF4Q1"
+constexpr uint64_t kGgufQ5_0 = 0x3054354655474700ull;  // "\0GGUF5Q0"
+constexpr uint64_t kGgufQ5_1 = 0x3154354655474700ull;  // "\0GGUF5Q1"
+constexpr uint64_t kGgufQ8_0 = 0x3054384655474700ull;  // "\0GGUF8Q0"
+// the activation quantizer of the weight's int8 arithmetic (its vec_dot_type, ne_layers.c:266-318): 0 the kblock
+// core's u8, 1 Q8_0 (Q4_0, Q5_0, Q8_0), 2 Q8_1 (Q4_1, Q5_1)
+int gguf_act_quant(const nad::DeviceWeight& w);
+bool int8_compute(const nad::DeviceWeight& w);  // a forward of this weight takes the int8 arithmetic right now
+
+// ------------------------------------------------------------------------------------------------ load (capi_load.hip)
+// base: the host blob, scanned for codes the device cannot hold (load time only; null skips the scan)
+bool blob_supported(const nad::Blob& b, const void* base, std::string* err);
+inline bool blob_supported(const nad::Blob& b, std::string* err) { return blob_supported(b, nullptr, err); }
+
+// ------------------------------------------------------------------------------------------------ forward calls
+// One forward as three values (capi_forward.hip): the activations, what happens to the product, where it goes.
+struct Act {
+  const void* p;
+  int t;  // ActType
+  int ld, m, k;
+};
+
+struct Epi {  // the default value: no epilogue
+  int kind = nad::kEpiNone;
+  const float* bias = nullptr;  // bias[m * bias_ld + n] (bias_ld = 0 broadcasts one row)
+  int bias_ld = 0;
+  const float* res = nullptr;
+  int ld_res = 0;
+  float* aux = nullptr;  // dual kinds: optional output of the gate activation; SILU_MUL of one weight: the multiplier
+  int ld_aux = 0;
+
+  bool is_dual() const { return kind == nad::kEpiSiluMul || kind == nad::kEpiGeluMul; }
+  // the gate activation alone of a dual kind (the first pass of a two-pass gate/up)
+  static Epi gate_of(int dual_kind) {
+    Epi e;
+    e.kind = dual_kind == nad::kEpiSiluMul ? nad::kEpiSilu : nad::kEpiGelu;
+    return e;
+  }
+  // the product times aux (the second pass; the activation is in aux already)
+  static Epi mul(float* aux, int ld_aux) {
+    Epi e;
+    e.kind = nad::kEpiSiluMul;
+    e.aux = aux;
+    e.ld_aux = ld_aux;
+    return e;
+  }
+};
+
+// fp16 result / SiLU*mul operand of a pipelined GEMM (the FFN's intermediates, ffn16_ok)
+struct Half16 {
+  _Float16* out = nullptr;
+  int ldo = 0;
+  const _Float16* aux = nullptr;
+};
+
+struct Out {
+  float* p;
+  int ld;
+  const Half16* h16 = nullptr;  // set: the result goes there as fp16 instead (p is not written)
+};
+
+// f16_tmp: the prefill may keep tmp1 / tmp2 as fp16 scratch (ffn16_ok); the reference-named host entries, whose
+// tmp2 the caller reads back as the fp32 intermediate (ip_fusion_ffn.cpp), pass false
+int ffn_forward(const void* act, int act_dtype, const void* w1p, const void* w2p, const void* w3p, float* tmp1,
+                float* tmp2, float* out, int m, int fin, int fmid, int fout, int lda, int epi, void* queue,
+                bool f16_tmp);
+
+#pragma GCC visibility pop
+
+extern "C" size_t nad_device_workspace_size(int m, int k);  // ne_ops.hip (include/neural_amd_ne.h)

@@ -475,7 +475,7 @@ extern "C" size_t nad_device_workspace_size(int m, int k) {
   const size_t kp = (size_t(k) + 255) / 256 * 256;
   auto a256 = [](size_t x) { return (x + 255) / 256 * 256; };
   // fp16 copy of A (tile padded), then the split-K partials of a GEMM with few output tiles (bound for any N); the
-  // mid-M kernel's K-run slabs (ks x N <= 32768 fp32 per row, capi.hip run_mid) fit the same m x 128 KiB
+  // mid-M kernel's K-run slabs (ks x N <= 32768 fp32 per row, capi_forward.hip run_mid) fit the same m x 128 KiB
   const size_t nbm = (size_t(m) + 255) / 256;
   const size_t gemm = a256(size_t(m) * kp * 2) + size_t(m) * 4 * 256 * 128 / nbm + 256;
   // m <= 16: the fp decode GEMV stages its activations in LDS; a weight in the int8-compute mode quantizes them into

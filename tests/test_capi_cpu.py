@@ -255,6 +255,18 @@ def test_plan_forward_kernel_choice():
     assert p(8, 4096, 4096, 128, m=2048)["fold"] and p(2, 4096, 4096, 128, m=2048)["fold"]
 
 
+def test_plan_mid_keeps_whole_4_stripe_geometry(knob):
+    """The mid-M kernel's automatic 8-stripe form (NAD_MID_WIDE=2) is dropped where its grid does not fit the CUs either:
+    int4 g64, N = 40960, K = 4096, M = 32 gives 640 x 1 workgroups of 4 stripes and 320 > 256 of 8.  The geometry that
+    stays is the 4-stripe one whole -- the plan reports the launched kernel's 512 threads, not the rejected form's
+    256 -- so it equals the plan under NAD_MID_WIDE=0 field for field."""
+    p = bestla.plan_forward
+    auto = p(4, 40960, 4096, 64, m=32)
+    assert (auto["kernel"], auto["grid"], auto["threads"]) == ("woq_mid_kernel", 640, 512), auto
+    knob("NAD_MID_WIDE", "0")
+    assert p(4, 40960, 4096, 64, m=32) == auto
+
+
 def test_plan_gemm4_waves_split_over_k(knob):
     """gemm4's K-split wave layout (NAD_GEMM4_KSW=2, auto): on for more than one round of output tiles or K >= 8192
     (gate, down, lm_head, M = 4096), off for one round at K = 4096 (profiles/r04_gemm4_ksw_ab.txt) and under split-K.

@@ -1,7 +1,7 @@
 """Prefill GEMMs (woq_gemm2.hip): gemm3 (default: every operand by LDS-DMA, three 64-deep half steps in flight) and
 gemm2 (NAD_GEMM_KERNEL=2: A by LDS-DMA one K step ahead, B in registers).
 
-Both run for int4 weights with group size a power-of-two multiple of 128 and M > 16 (capi.hip gemm2_ok); these
+Both run for int4 weights with group size a power-of-two multiple of 128 and M > 16 (capi_forward.hip gemm2_ok); these
 cases pin them against the oracle (fp64 GEMM on the reference's dequantized weights) on ragged M/N, K tails, all
 scale dtypes, asymmetric zero points, per-channel scales and act-order shuffles.
 
@@ -315,7 +315,7 @@ def test_gemm4_takes_the_fallback_configs(oracle, knob):
 
 
 SPLITK_CASES = [
-    # m, n, k, bs, asym, act -- few 256 x 128 output tiles: gemm3 runs split-K (capi.hip splitk_plan) + the ordered reduce
+    # m, n, k, bs, asym, act -- few 256 x 128 output tiles: gemm3 runs split-K (capi_forward.hip splitk_plan) + the ordered reduce
     (17, 4096, 4096, 128, False, "fp16"),     # smallest M past the GEMV (was the register-staged fallback)
     (31, 1024, 4096, 128, True, "fp32"),
     (64, 4096, 4096, 128, False, "fp32"),     # batched decode at the Llama O shape: 32 tiles x 8 runs of 4 K tiles
@@ -473,7 +473,7 @@ def test_gemm_mid_m(oracle, knob, m, fmt):
     (65504.0 / 8 * (1 + 2.0 ** -20), False),
 ])
 def test_fold_range_edge_scales(oracle, edge, folds):
-    """the load-time fold check (capi.hip scale_in_fold_range) at the edges of the fp16 range.  A
+    """the load-time fold check (capi_load.hip scale_in_fold_range) at the edges of the fp16 range.  A
     blob whose group scales sit exactly on an edge folds q * s into fp16 (gemm7) and is held to FOLD_TOL; one just past
     it runs the exact fp32 group-scale path (gemm3) and is held to the fp16-activation bar, both against the oracle."""
     m, n, k, g = 128, 256, 1024, 128
