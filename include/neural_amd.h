@@ -167,7 +167,9 @@ void nad_reload_knobs(void);
 /* blob header summary (same fields as the oracle's orc_blob_info) */
 int nad_blob_info(const void* hostblob, int64_t* out27);
 /* Y = epi(X . W^T): X in fp32/fp16/bf16 (act_dtype), Y fp32.  bias: bias[m*bias_ld + n] (bias_ld 0 = broadcast);
- * res: residual[m*ld_res + n] for NAD_EPI_RES_ADD. */
+ * res: residual[m*ld_res + n] for NAD_EPI_RES_ADD.  Writes exactly out[0:m, 0:n] (row stride ldo), whatever out held;
+ * reads X, bias and res only inside their [m][k] / [m][n] windows.  A null bias / res for an epilogue that needs it is
+ * an error (-1), found before anything else is looked at. */
 int nad_device_forward(const void* act, int act_dtype, const void* devstor, float* out, int m, int n, int k, int lda,
                        int ldo, int epi, const float* bias, int bias_ld, const float* res, int ld_res, void* queue);
 /* Dry run of nad_device_forward for a weight geometry (bits 2 / 4 / 8, blocksize <= 0 = per-channel, scale_t

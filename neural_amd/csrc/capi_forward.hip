@@ -710,8 +710,6 @@ static int forward_any(const Act& x, const DeviceWeight& w, const Out& o, const 
 extern "C" int nad_device_forward(const void* act, int act_dtype, const void* devstor, float* out, int m, int n, int k,
                                   int lda, int ldo, int epi, const float* bias, int bias_ld, const float* res,
                                   int ld_res, void* queue) {
-  const DeviceWeight* w = as_weight(devstor);
-  if (!w || !check_shape(*w, m, n, k, lda, ldo)) return -1;
   Epi e;
   e.kind = epi;
   e.bias = bias;
@@ -726,6 +724,12 @@ extern "C" int nad_device_forward(const void* act, int act_dtype, const void* de
     set_err("bias epilogue without bias");
     return -1;
   }
+  if (epi == kEpiResAdd && !res) {
+    set_err("residual epilogue without residual");
+    return -1;
+  }
+  const DeviceWeight* w = as_weight(devstor);
+  if (!w || !check_shape(*w, m, n, k, lda, ldo)) return -1;
   return forward_any(Act{act, act_dtype, lda, m, k}, *w, Out{out, ldo}, e, static_cast<hipStream_t>(queue));
 }
 

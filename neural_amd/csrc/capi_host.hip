@@ -165,7 +165,20 @@ struct HostBuf {
   size_t bytes;
   bool out;
   void* dev;
+  // an output of `rows` rows of `width` bytes, `pitch` bytes apart (pitch > width): only those come back, the
+  // caller's bytes between the rows stay as they are.  rows = 0: one flat span of `bytes`.
+  size_t rows = 0, width = 0, pitch = 0;
 };
+// the staged form of an output matrix [rows][n] fp32 with row stride ld: flat when contiguous
+HostBuf out_buf(float* p, size_t rows, int n, int ld) {
+  HostBuf b{p, (rows - 1) * size_t(ld) * 4 + size_t(n) * 4, true, nullptr};
+  if (ld > n) {
+    b.rows = rows;
+    b.width = size_t(n) * 4;
+    b.pitch = size_t(ld) * 4;
+  }
+  return b;
+}
 int with_staged(std::vector<HostBuf>& bufs, hipStream_t st) {
   size_t total = 0;
   for (auto& b : bufs)
@@ -191,8 +204,13 @@ int with_staged(std::vector<HostBuf>& bufs, hipStream_t st) {
 }
 int finish_staged(std::vector<HostBuf>& bufs, hipStream_t st) {
   for (auto& b : bufs)
-    if (b.out && b.host && b.dev != b.host)
-      HIP_OK(hipMemcpyAsync(const_cast<void*>(b.host), b.dev, b.bytes, hipMemcpyDeviceToHost, st));
+    if (b.out && b.host && b.dev != b.host) {
+      if (b.rows)
+        HIP_OK(hipMemcpy2DAsync(const_cast<void*>(b.host), b.pitch, b.dev, b.pitch, b.width, b.rows,
+                                hipMemcpyDeviceToHost, st));
+      else
+        HIP_OK(hipMemcpyAsync(const_cast<void*>(b.host), b.dev, b.bytes, hipMemcpyDeviceToHost, st));
+    }
   HIP_OK(hipStreamSynchronize(st));
   return 0;
 }
@@ -229,7 +247,7 @@ static int host_forward(float* act, void* wblob, float* out, int m, int n, int k
   if (!w) return -1;
   NadDevice* d = host_device();
   std::vector<HostBuf> bufs = {{act, size_t(m - 1) * lda * 4 + size_t(k) * 4, false, nullptr},
-                               {out, size_t(m - 1) * ldo * 4 + size_t(n) * 4, true, nullptr},
+                               out_buf(out, size_t(m), n, ldo),
                                {bias, bias ? (bias_ld ? size_t(m - 1) * bias_ld * 4 + size_t(n) * 4 : size_t(n) * 4) : 0,
                                 false, nullptr}};
   if (with_staged(bufs, d->stream)) return -1;
@@ -292,9 +310,9 @@ extern "C" void bestla_fusion_QKV_f32f32_forward(float* activation, void* wqptr,
     return;
   }
   NadDevice* d = host_device();
-  const size_t obytes = size_t(3) * _m * ldo * 4;
+  // the three matrices lie m * ldo floats apart: 3 m rows of one pitch
   std::vector<HostBuf> bufs = {{activation, size_t(_m - 1) * lda * 4 + size_t(_k) * 4, false, nullptr},
-                               {output, obytes, true, nullptr}};
+                               out_buf(output, size_t(3) * _m, _n, ldo)};
   if (with_staged(bufs, d->stream)) {
     report("bestla_fusion_QKV_f32f32_forward");
     return;

@@ -310,3 +310,26 @@ def test_host_cost_per_forward_under_3us():
         base = per_call(3, n, k, g, m)
         cost = per_call(bits, n, k, g, m)
         assert cost - base < 3e-6 and cost < 20e-6, (bits, n, k, m, cost, base)
+
+
+def test_residual_epilogue_without_residual_is_an_error():
+    """nad_device_forward validates the epilogue's arguments before it looks at the weight: RES_ADD with a null residual
+    returns -1 with its own message (as BIAS / ADD_GELU with a null bias do), and nothing is launched -- the descriptor
+    here is all zeros, no weight at all."""
+    L = _lib.lib()
+    desc = (C.c_uint8 * L.bestla_device_storage_size())()
+    x = np.zeros((1, 32), np.float32)
+    y = np.zeros((1, 16), np.float32)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    for epi, bias, msg in ((bestla.EPI_RES_ADD, vp(y), "residual epilogue without residual"),
+                           (bestla.EPI_BIAS, None, "bias epilogue without bias"),
+                           (bestla.EPI_ADD_GELU, None, "bias epilogue without bias")):
+        L.nad_clear_error()
+        rc = L.nad_device_forward(vp(x), bestla.ACT_F32, desc, vp(y), 1, 16, 32, 32, 16, epi, bias, 0, None, 0, None)
+        assert rc == -1
+        assert msg in _lib.last_error(), _lib.last_error()
+    # with its arguments in place the call gets as far as the (missing) weight, and says so
+    L.nad_clear_error()
+    rc = L.nad_device_forward(vp(x), bestla.ACT_F32, desc, vp(y), 1, 16, 32, 32, 16, bestla.EPI_RES_ADD, None, 0, vp(y),
+                              16, None)
+    assert rc == -1 and "residual" not in _lib.last_error() and _lib.last_error() != ""

@@ -356,3 +356,128 @@ def test_per_weight_compute_mode(oracle, m):
     assert ws[2].compute == bestla.COMPUTE_FP
     ws[1].set_compute(None)
     assert ws[1].compute == bestla.COMPUTE_FP
+
+
+# ------------------------------------------------------------------------------------------------ strided host buffers
+# The host-pointer entries with lda > k and ldo > n, as an NE graph calls them when a mul_mat result is a view of a
+# wider tensor: the reference's CPU kernels write [m][n] only (inner_product.cpp, ip_fusion_qkv.cpp), so every host
+# byte outside the output windows must come back untouched.  Host buffers are canaried as tests/edges.py canaries the
+# device ones: one quiet-NaN bit pattern everywhere, compared bit for bit as int32 after the call; the activation and
+# bias padding is NaN.
+H_CANARY = 0x7FC0BEEF
+H_GUARD = 2
+
+
+class _HostOut:
+    """[H_GUARD + rows + H_GUARD][ld] canary-filled fp32; the windows are [m][n] blocks at the given first rows"""
+
+    def __init__(self, rows, ld):
+        self.ld = ld
+        self.bits = np.full(((H_GUARD + rows + H_GUARD), ld), H_CANARY, np.int32)
+        self.f32 = self.bits.view(np.float32)
+        self.inside = np.zeros(self.bits.shape, bool)
+
+    def window(self, row0, m, n):
+        self.inside[H_GUARD + row0:H_GUARD + row0 + m, :n] = True
+        return self.f32[H_GUARD + row0:H_GUARD + row0 + m, :n]
+
+    def ptr(self, row0=0):
+        return C.c_void_p(self.f32.ctypes.data + (H_GUARD + row0) * self.ld * 4)
+
+    def check(self):
+        assert not np.isnan(self.f32[self.inside]).any(), "NaN inside an output window"
+        wrong = np.flatnonzero(self.bits[~self.inside] != H_CANARY)
+        assert wrong.size == 0, f"{wrong.size} host element(s) outside the output windows overwritten"
+
+
+def _host_padded(values, ld):
+    """fp32 [m][c] values inside a NaN-filled [m][ld] host array -> (storage, window)"""
+    m, c = values.shape
+    store = np.full((m, ld), np.nan, np.float32)
+    store[:, :c] = values
+    return store, store[:, :c]
+
+
+@pytest.mark.parametrize("m", [3, 20])
+@pytest.mark.parametrize("entry", ["f32f32", "add_bcast", "add_row", "batch"])
+def test_host_abi_strided_buffers(oracle, entry, m):
+    L = _lib.lib()
+    n, k = 97, 512
+    lda, ldo = k + 8, n + 5
+    blob = _wb(oracle, n, k, 61)
+    rng = np.random.default_rng(m)
+    A = rng.uniform(-1, 1, size=(m, k)).astype(np.float32)
+    a_store, _ = _host_padded(A, lda)
+    ref = oracle.forward(A, blob, n, k).astype(np.float64)
+    scale = np.abs(ref).max()
+    out = _HostOut(m, ldo)
+    y = out.window(0, m, n)
+    L.nad_clear_error()
+    if entry == "f32f32":
+        L.bestla_f32f32_forward(vp(a_store), vp(blob), out.ptr(), m, n, k, lda, ldo, None)
+    elif entry == "batch":
+        P = type("P", (C.Structure,), {"_fields_": [("A", C.c_void_p), ("B", C.c_void_p), ("C", C.c_void_p),
+                                                     ("lda", C.c_int), ("ldc", C.c_int)]})
+        arr = (P * 1)(P(vp(a_store).value, vp(blob).value, out.ptr().value, lda, ldo))
+        assert L.BTLAGemmBatchDriver(m, n, k, 1, C.cast(arr, C.c_void_p), None, None)
+    else:
+        bcast = entry == "add_bcast"
+        bias = (rng.uniform(-1, 1, size=(n,) if bcast else (m, n)) * scale).astype(np.float32)
+        # per-row bias: read with the OUTPUT's row stride (inner_product.cpp:132-244)
+        b_store = bias if bcast else _host_padded(bias, ldo)[0]
+        L.bestla_fusion_add_f32f32_forward(vp(a_store), vp(blob), vp(b_store), out.ptr(), m, n, k, lda, ldo, bcast,
+                                           None)
+        ref = ref + bias
+    assert _lib.last_error() == ""
+    out.check()
+    err = float(np.abs(y - ref).max() / scale)
+    assert err <= (2e-5 if m <= 16 else 1e-3), err
+    L.nad_host_cache_clear()
+
+
+@pytest.mark.parametrize("m", [3, 20])
+def test_host_abi_strided_qkv(oracle, m):
+    """Q, K, V at output + i * m * ldo: the canary sits in each matrix's padding columns and around the three"""
+    L = _lib.lib()
+    n, k = 97, 512
+    lda, ldo = k + 8, n + 5
+    blobs = [_wb(oracle, n, k, 70 + i) for i in range(3)]
+    A = np.random.default_rng(m).uniform(-1, 1, size=(m, k)).astype(np.float32)
+    a_store, _ = _host_padded(A, lda)
+    out = _HostOut(3 * m, ldo)
+    ys = [out.window(i * m, m, n) for i in range(3)]
+    L.nad_clear_error()
+    L.bestla_fusion_QKV_f32f32_forward(vp(a_store), vp(blobs[0]), vp(blobs[1]), vp(blobs[2]), out.ptr(), m, n, k, lda,
+                                       ldo, None)
+    assert _lib.last_error() == ""
+    out.check()
+    for y, b in zip(ys, blobs):
+        assert _rel_err(y, oracle.forward(A, b, n, k)) <= (2e-5 if m <= 16 else 1e-3)
+    L.nad_host_cache_clear()
+
+
+@pytest.mark.parametrize("m", [3, 20])
+def test_host_abi_ffn_add_gelu_per_row_bias(oracle, m):
+    """FFN_Add_GeLu with boardcast_bias = false: b1 [m][fmid] and b2 [m][fout] added row by row; tmp1 and the output
+    (contiguous, as the entry has no strides) lie inside canaried host buffers."""
+    L = _lib.lib()
+    fin, fmid, fout = 512, 200, 97
+    b1, b2 = _wb(oracle, fmid, fin, 81), _wb(oracle, fout, fmid, 82)
+    rng = np.random.default_rng(m)
+    A = rng.uniform(-1, 1, size=(m, fin)).astype(np.float32)
+    bias1 = rng.uniform(-0.5, 0.5, size=(m, fmid)).astype(np.float32)
+    bias2 = rng.uniform(-0.5, 0.5, size=(m, fout)).astype(np.float32)
+    t1, o = _HostOut(m, fmid), _HostOut(m, fout)
+    tmp1, out = t1.window(0, m, fmid), o.window(0, m, fout)
+    assert L.bestla_fusion_FFN_Add_GeLu_f32f32_support(vp(b1), vp(b2), m, fin, fmid, fout)
+    L.nad_clear_error()
+    L.bestla_fusion_FFN_Add_GeLu_f32f32_forward(vp(A), vp(b1), vp(b2), vp(bias1), vp(bias2), t1.ptr(), o.ptr(), m, fin,
+                                                fmid, fout, False, None)
+    assert _lib.last_error() == ""
+    t1.check()
+    o.check()
+    h = _gelu(oracle.forward(A, b1, fmid, fin).astype(np.float64) + bias1)
+    ref = oracle.forward(h.astype(np.float32), b2, fout, fmid).astype(np.float64) + bias2
+    assert _rel_err(tmp1, h) <= (1e-4 if m <= 16 else 1e-3)
+    assert _rel_err(out, ref) <= (1e-4 if m <= 16 else 1e-3)
+    L.nad_host_cache_clear()
