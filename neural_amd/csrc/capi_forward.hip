@@ -127,14 +127,13 @@ static int prepare_gemv(GemvArgs& a, int& waves, int& grid, const Act& x, const 
   a.nt = w0.nt;
   a.ng = w0.ng;
   a.bs = w0.blocksize;
-  a.tpg_mask = tpg == 0 ? 0x7fffffff : tpg - 1;
   a.tpg_shift = tpg == 0 ? 31 : __builtin_ctz(unsigned(tpg));
   a.scale_t = w0.scale_t;
   a.asym = w0.asym;
   a.shuffle = w0.shuffle;
   a.a_fast = (vec_aligned(x) && w0.shuffle == nullptr && x.k % 8 == 0) ? 1 : 0;
   int stripes = 0;
-  for (int i = 0; i < 4; i++) a.stripe_base[i] = INT_MAX;
+  for (int i = 0; i < 3; i++) a.stripe_base[i] = INT_MAX;
   for (int i = 0; i < W.nw; i++) {
     a.w[i] = view(W[i], W.outs[i], W.ldos[i], e);
     a.stripe_base[i] = stripes;

@@ -35,6 +35,7 @@
 
 #include <climits>
 #include <cstdint>
+#include <type_traits>
 
 #include "woq_device.h"
 #include "woq_kernels.h"
@@ -63,17 +64,6 @@ __device__ unsigned long long nad_trace_buf[kTraceSlots][kTraceMaxWg];
 #define NAD_TRACE_MAX(slot) \
   do {                      \
   } while (0)
-#endif
-
-// M = 1 kernel tail: partial-sum slots laid out per column so a 16-wave launch reduces with four 16-B LDS reads per
-// output and no per-slot clamps (the general form's 16 clamped offsets + masks are ~100 scalar instructions executed
-// once per launch, cold in the instruction cache: ~0.4 us per KB).  Measured (profiles/r06_gemv_tail_ab.txt, same
-// box, alternating): O 4.80 -> 4.55 us, decode 946-951 -> 969-972 tok/s; bit-identical sums (same order).  A
-// branch-free first weight stage (the two-armed load_stage makes hipcc wait vmcnt(0) for the activation loads before
-// the first weight load) measured neutral (943-947 tok/s) on this kernel and was not kept here; woq_gemv_m1s_kernel
-// below, which serves the decode token's launches, has no control flow around any stage's loads.
-#ifndef NAD_GEMV_LEAN_TAIL
-#define NAD_GEMV_LEAN_TAIL 1
 #endif
 
 constexpr int kOOB = 0x7FFF0000;  // a buffer offset past every resource: the load returns 0 and touches no memory
@@ -131,7 +121,35 @@ struct StageRegs {
 #ifndef NAD_TILE_AUX
 #define NAD_TILE_AUX 2  // non-temporal: the weights are read once per token
 #endif
-// Issue one stage's loads (never predicated: past-the-end tiles / stages get the out-of-range offset), then advance.
+// The loads of the stage at the cursor: KSN tiles at immediate offsets from one stripe base, each with its GPT group
+// scales (+ zero points).  Never predicated: tiles and groups past the end of K -- and, with `on` false, the whole
+// stage -- take the out-of-range offset.  Shared by both stage loaders below.
+template <bool ASYM, int GPT, int KSN, class Args>
+__device__ __forceinline__ void stage_loads(const Args& a, StageRegs<GPT, KSN>& S, const StageCursor& c, bool on,
+                                            int lane, int vs) {
+  const int nt = a.nt, ng = a.ng;
+  const int t0 = c.q * KSN;
+  const int tb = (c.s * nt + t0) * 1024;
+  const int rowb = a.scale_t == kScaleF32 ? 64 : 32;  // bytes per scale row of 16
+#pragma unroll
+  for (int i = 0; i < KSN; i++) {
+    const bool live = on && t0 + i < nt;
+    S.b[i] = __builtin_bit_cast(u4_t, __builtin_amdgcn_raw_buffer_load_b128(c.rt, (live ? tb + i * 1024 : kOOB) + lane * 16, 0, NAD_TILE_AUX));
+#pragma unroll
+    for (int g = 0; g < GPT; g++) {
+      const int grp = GPT == 1 ? ((t0 + i) >> a.tpg_shift) : (t0 + i) * GPT + g;
+      const bool gl = live && (GPT == 1 || grp < ng);
+      const int row = c.s * ng + grp;
+      S.sc[i][g] = __builtin_amdgcn_raw_buffer_load_b32(c.rs, (gl ? row * rowb : kOOB) + vs, 0, 0);
+      if constexpr (ASYM)
+        S.zp[i][g] = int(int8_t(__builtin_amdgcn_raw_buffer_load_b8(c.rz, (gl ? row * 16 : kOOB) + (lane & 15), 0, 0)));
+      else
+        S.zp[i][g] = 0;
+    }
+  }
+}
+
+// Issue one stage's loads, then advance.  Two-armed: a past-the-end stage issues the same loads, all out of range.
 template <int GPT, bool ASYM, int KSN = KS>
 __device__ __forceinline__ void load_stage(const GemvArgs& a, StageRegs<GPT, KSN>& S, StageCursor& c, int nv, int nsl,
                                            int wave, int NW, int v0, int lane, int vs) {
@@ -147,27 +165,7 @@ __device__ __forceinline__ void load_stage(const GemvArgs& a, StageRegs<GPT, KSN
     }
     return;
   }
-  const int nt = a.nt, ng = a.ng;
-  const bool over = false;
-  const int t0 = c.q * KSN;
-  const int tb = (c.s * nt + t0) * 1024;
-  const int rowb = a.scale_t == kScaleF32 ? 64 : 32;  // bytes per scale row of 16
-#pragma unroll
-  for (int i = 0; i < KSN; i++) {
-    const bool live = !over && t0 + i < nt;
-    S.b[i] = __builtin_bit_cast(u4_t, __builtin_amdgcn_raw_buffer_load_b128(c.rt, (live ? tb + i * 1024 : kOOB) + lane * 16, 0, NAD_TILE_AUX));
-#pragma unroll
-    for (int g = 0; g < GPT; g++) {
-      const int grp = GPT == 1 ? ((t0 + i) >> a.tpg_shift) : (t0 + i) * GPT + g;
-      const bool gl = live && (GPT == 1 || grp < ng);
-      const int row = c.s * ng + grp;
-      S.sc[i][g] = __builtin_amdgcn_raw_buffer_load_b32(c.rs, (gl ? row * rowb : kOOB) + vs, 0, 0);
-      if constexpr (ASYM)
-        S.zp[i][g] = int(int8_t(__builtin_amdgcn_raw_buffer_load_b8(c.rz, (gl ? row * 16 : kOOB) + (lane & 15), 0, 0)));
-      else
-        S.zp[i][g] = 0;
-    }
-  }
+  stage_loads<ASYM>(a, S, c, true, lane, vs);
   c.q += NW;
   if (c.q >= nsl) {
     c.q = wave;
@@ -190,6 +188,7 @@ __device__ __forceinline__ void load_stage(const GemvArgs& a, StageRegs<GPT, KSN
 struct Dq4 {
   uint32_t m0, m1, mag;  // masks and magic, kept in registers (VOP3 takes no literals on gfx9)
   h2_t s16;
+  h2_t c0, c1;           // -(1024 + bias) and -(64 + bias): the symmetric weights' zero point folded into the magic's
 };
 
 // (x & m) | c in one VOP3 instruction (hipcc splits it when both constants sit in SGPRs: one constant-bus read on gfx9)
@@ -242,6 +241,104 @@ __device__ __forceinline__ float scale_to_f32(uint32_t x, int st, int sh) {
   else if constexpr (ST == kScaleF32) return __uint_as_float(x);
   else if constexpr (ST == kScaleBF16) return __uint_as_float((x >> sh) << 16);
   else return f16_bits_to_f32(uint16_t(x >> sh));
+}
+
+constexpr int k_tile(int bits) { return bits == 4 ? 128 : (bits == 2 ? 256 : 64); }  // k per 1 KiB tile
+constexpr int zp_bias(int bits) { return bits == 4 ? 8 : (bits == 2 ? 2 : 128); }
+
+// the launch's int4 constants; mask and magic arrive as kernel arguments so that they stay in scalar registers
+template <int BITS>
+__device__ __forceinline__ Dq4 dq4_consts(uint32_t mask, uint32_t magic) {
+  Dq4 q;
+  q.m0 = __builtin_amdgcn_readfirstlane(mask);
+  q.m1 = q.m0 << 4;
+  q.mag = __builtin_amdgcn_readfirstlane(magic);
+  q.s16 = splat(1.f / 16.f);
+  q.c0 = splat(-(1024.f + zp_bias(BITS)));
+  q.c1 = splat(-(64.f + zp_bias(BITS)));
+  return q;
+}
+
+// the 8 weights (q - zero point, exact fp16) a lane feeds MFMA step d of a tile
+template <int BITS, bool ASYM>
+__device__ __forceinline__ h8_t dequant_tile_step(const u4_t& b, int d, int zp, const Dq4& dq) {
+  if constexpr (BITS == 4) {
+    if constexpr (ASYM) {
+      const float z = float(zp);
+      return dequant4(b[d], dq, dq.c0 - splat(z), dq.c1 - splat(z));
+    } else {
+      return dequant4(b[d], dq, dq.c0, dq.c1);
+    }
+  } else {
+    return BITS == 2 ? dequant2_step(b, d, zp_bias(BITS) + zp) : dequant_step<BITS>(b, d, zp_const(zp_bias(BITS) + zp));
+  }
+}
+
+// One stage's arithmetic, shared by every kernel of this file: KSN independent MFMA chains (one per tile, step-major)
+// so the scheduler can interleave them; at each group end the tiles' group partials are scaled into the stripe sum
+// `acc`, in tile order.  ab + tile_off(i): this lane's activation row at tile i of the stage; LO adds the second MFMA
+// over the fp16 lo row at abl (woq_gemv_kernel with more than 8 fp32 / bf16 rows).
+template <int BITS, int GPT, bool ASYM, int KSN, int ST, bool LO, class TileOff>
+__device__ __forceinline__ void stage_mac(const StageRegs<GPT, KSN>& S, const Dq4& dq, const char* ab, const char* abl,
+                                          TileOff tile_off, int scale_t, int ssh, f4_t& acc) {
+  constexpr int SPT = k_tile(BITS) / 32, SPG = SPT / GPT;  // MFMA steps per tile, per group
+  f4_t accg[KSN];
+#pragma unroll
+  for (int d = 0; d < SPT; d++) {
+    const int g = GPT == 1 ? 0 : d / SPG;
+#pragma unroll
+    for (int i = 0; i < KSN; i++) {
+      const h8_t bf = dequant_tile_step<BITS, ASYM>(S.b[i], d, S.zp[i][g], dq);
+      const h8_t af = *reinterpret_cast<const h8_t*>(ab + tile_off(i) + d * 64);
+      accg[i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af, bf, d % SPG == 0 ? f4_t{0.f, 0.f, 0.f, 0.f} : accg[i], 0, 0, 0);
+      if constexpr (LO) {
+        const h8_t afl = *reinterpret_cast<const h8_t*>(abl + tile_off(i) + d * 64);
+        accg[i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(afl, bf, accg[i], 0, 0, 0);
+      }
+    }
+    if ((d + 1) % SPG == 0) {
+#pragma unroll
+      for (int i = 0; i < KSN; i++) acc += accg[i] * scale_to_f32<ST>(S.sc[i][g], scale_t, ssh);
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ slot reduction
+// A wave's partial sum of a stripe goes to an LDS slot; after the barrier each output sums its slots in wave order:
+// s_i sums slots i, i + 4, ... of the whole groups of four, s_0 takes the rest, then (s0 + s1) + (s2 + s3).
+// The M = 1 kernels' form: at most 16 adjacent slots, all read at once (one LDS round trip) at offsets clamped to the
+// last slot.  woq_gemv_kernel keeps the same order as a loop of its own (step 4 there says why).
+__device__ __forceinline__ float reduce_slots(const float* ps, int nwl) {
+  float t[16];
+#pragma unroll
+  for (int w = 0; w < 16; w++) t[w] = ps[min(w, nwl - 1)];
+  const int full = nwl & ~3;
+  float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+#pragma unroll
+  for (int w = 0; w < 16; w += 4)
+    if (w < full) {
+      s0 += t[w];
+      s1 += t[w + 1];
+      s2 += t[w + 2];
+      s3 += t[w + 3];
+    }
+#pragma unroll
+  for (int w = 0; w < 16; w++)
+    if (w >= full && w < nwl) s0 += t[w];
+  return (s0 + s1) + (s2 + s3);
+}
+
+// The M = 1 kernels lay their slots out per column, [nv][16 columns][NW], so that a launch of 16 waves with a K-slice
+// each reduces with four 16-B LDS reads per output and no per-slot clamps: the same order as reduce_slots at 16, whose
+// 16 clamped offsets + masks are ~100 scalar instructions executed once per launch, cold in the instruction cache
+// (~0.4 us per KB).  Measured (profiles/r06_gemv_tail_ab.txt, same box, alternating): O 4.80 -> 4.55 us, decode
+// 946-951 -> 969-972 tok/s; bit-identical sums.
+__device__ __forceinline__ float reduce16(const float* col) {
+  const float4* ps = reinterpret_cast<const float4*>(col);
+  const float4 t0 = ps[0], t1 = ps[1], t2 = ps[2], t3 = ps[3];
+  const float s0 = ((t0.x + t1.x) + t2.x) + t3.x, s1 = ((t0.y + t1.y) + t2.y) + t3.y;
+  const float s2 = ((t0.z + t1.z) + t2.z) + t3.z, s3 = ((t0.w + t1.w) + t2.w) + t3.w;
+  return (s0 + s1) + (s2 + s3);
 }
 
 // ------------------------------------------------------------------------------------------------ activation staging
@@ -315,10 +412,8 @@ constexpr int gemv_max_threads() {
 template <int BITS, int HILO, int GPT, bool ASYM, int NST>
 __global__ __launch_bounds__(gemv_max_threads<GPT>()) void woq_gemv_kernel(GemvArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int KT = BITS == 4 ? 128 : (BITS == 2 ? 256 : 64);
-  constexpr int SPT = KT / 32;
-  static_assert(SPT % GPT == 0, "groups must tile the K tile");
-  constexpr int SPG = SPT / GPT;  // steps per group when GPT > 1
+  constexpr int KT = k_tile(BITS);
+  static_assert(KT / 32 % GPT == 0, "groups must tile the K tile");
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6));
   const int NW = __builtin_amdgcn_readfirstlane(int(blockDim.x >> 6));
@@ -326,16 +421,6 @@ __global__ __launch_bounds__(gemv_max_threads<GPT>()) void woq_gemv_kernel(GemvA
   const int R = HILO == 0 ? M : 2 * M;
   const int nsl = (nt + KS - 1) / KS;  // K-slices per stripe
   NAD_TRACE(0);
-#ifdef NAD_EXP_KPREF
-  {  // touch every 64-B line of the argument block in one batch so the later scalar loads hit
-    const __attribute__((address_space(4))) uint32_t* kp =
-        (const __attribute__((address_space(4))) uint32_t*)__builtin_amdgcn_kernarg_segment_ptr();
-    uint32_t s = 0;
-#pragma unroll
-    for (int i = 0; i < int(sizeof(GemvArgs) + 63) / 64; i++) s ^= kp[i * 16];
-    asm volatile("; kpref %0" ::"s"(s));
-  }
-#endif
 
   // this workgroup's units (wave-uniform)
   const int G = gridDim.x, bid = blockIdx.x;
@@ -422,13 +507,7 @@ __global__ __launch_bounds__(gemv_max_threads<GPT>()) void woq_gemv_kernel(GemvA
   const char* a_hi = smem + size_t(row_hi) * Kp * 2 + kq * 16;
   const char* a_lo = smem + size_t(row_lo) * Kp * 2 + kq * 16;
   const int ssh = a.scale_t == kScaleF32 ? 0 : (lane & 1) * 16;  // this lane's half of a 16-bit scale pair
-  constexpr int BIAS = BITS == 4 ? 8 : (BITS == 2 ? 2 : 128);
-  Dq4 dq;
-  dq.m0 = __builtin_amdgcn_readfirstlane(a.dq_mask);
-  dq.m1 = dq.m0 << 4;
-  dq.mag = __builtin_amdgcn_readfirstlane(a.dq_magic);
-  dq.s16 = splat(1.f / 16.f);
-  const h2_t zc0 = splat(-(1024.f + BIAS)), zc1 = splat(-(64.f + BIAS));
+  const Dq4 dq = dq4_consts<BITS>(a.dq_mask, a.dq_magic);
 
   f4_t acc = {0.f, 0.f, 0.f, 0.f};
   int cj = idle ? nv : 0, cq = wave;  // compute cursor (wave-uniform)
@@ -436,42 +515,11 @@ __global__ __launch_bounds__(gemv_max_threads<GPT>()) void woq_gemv_kernel(GemvA
   auto compute_stage = [&](const StageRegs<GPT>& S) {
     if (cj >= nv) return;
     const int t0 = cq * KS;
-    const char* ab = a_hi + t0 * KT * 2;
-    const char* abl = a_lo + t0 * KT * 2;
-    // KS independent MFMA chains (one per tile, step-major) so the scheduler can interleave them; tiles past the end
-    // of K carry out-of-range (zero) weights and a zero scale, and read a valid activation row (no NaN from LDS).
-    f4_t accg[KS];
-#pragma unroll
-    for (int d = 0; d < SPT; d++) {
-      const int g = GPT == 1 ? 0 : d / SPG;
-#pragma unroll
-      for (int i = 0; i < KS; i++) {
-        const int ti = min(t0 + i, nt - 1) - t0;
-        h8_t bf;
-        if constexpr (BITS == 4) {
-          if constexpr (ASYM) {
-            const float z = float(S.zp[i][g]);
-            bf = dequant4(S.b[i][d], dq, zc0 - splat(z), zc1 - splat(z));
-          } else {
-            bf = dequant4(S.b[i][d], dq, zc0, zc1);
-          }
-        } else {
-          bf = BITS == 2 ? dequant2_step(S.b[i], d, BIAS + S.zp[i][g])
-                         : dequant_step<BITS>(S.b[i], d, zp_const(BIAS + S.zp[i][g]));
-        }
-        const h8_t af = *reinterpret_cast<const h8_t*>(ab + ti * KT * 2 + d * 64);
-        const bool first = d % SPG == 0;
-        accg[i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af, bf, first ? f4_t{0.f, 0.f, 0.f, 0.f} : accg[i], 0, 0, 0);
-        if constexpr (HILO == 2) {
-          const h8_t afl = *reinterpret_cast<const h8_t*>(abl + ti * KT * 2 + d * 64);
-          accg[i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(afl, bf, accg[i], 0, 0, 0);
-        }
-      }
-      if ((d + 1) % SPG == 0) {  // group end: scale each tile's group partial into the stripe sum, in tile order
-#pragma unroll
-        for (int i = 0; i < KS; i++) acc += accg[i] * scale_bits_to_f32(S.sc[i][g], a.scale_t, ssh);
-      }
-    }
+    // tiles past the end of K carry out-of-range (zero) weights and a zero scale, and read a valid activation row (no
+    // NaN from LDS)
+    stage_mac<BITS, GPT, ASYM, KS, -1, HILO == 2>(
+        S, dq, a_hi + t0 * KT * 2, a_lo + t0 * KT * 2, [&](int i) { return (min(t0 + i, nt - 1) - t0) * KT * 2; },
+        a.scale_t, ssh, acc);
     cq += NW;
     if (cq >= nsl) {  // this wave's last slice of stripe cj: publish its partial
       f4_t r = acc;
@@ -510,6 +558,9 @@ __global__ __launch_bounds__(gemv_max_threads<GPT>()) void woq_gemv_kernel(GemvA
 #pragma unroll
     for (int h = 0; h < 2; h++) {
       if (h < vpu) {
+        // reduce_slots' order as a loop over the live slots (slots M * 16 floats apart).  Kept as this kernel's own
+        // copy: reading 16 clamped slots per output, as reduce_slots does, measured 1-2.5 % slower here, where a
+        // thread reduces M outputs per stripe (N = 11008 M = 8 fp16: 12.1 -> 12.4 us).
         const float* ps = part + (size_t(p * vpu + h) * NW * M + mm) * 16 + nn;
         const size_t wst = size_t(M) * 16;
         float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
@@ -619,48 +670,54 @@ static bool lean_ok(const GemvArgs& a, int bits, int waves) {
 #define NAD_M1_DUAL_NST 2
 #endif
 
-template <int BITS, int GPT, int AT, bool ASYM, int KSN, int SPW, bool BATCH, int NST, int ST = -1>
-__device__ __forceinline__ void m1_body(GemvArgs& a, int bid) {
+// Steps 1-3 of both M = 1 kernels -- this wave's activation loads, its first weight stage, the staging into its LDS
+// rows, the remaining ring stages, and the compute loop up to the published partial sums and the one barrier -- exist
+// once, here.  What differs between woq_gemv_m1_kernel and woq_gemv_m1s_kernel comes in as the policy P:
+//   P::Args                       the argument block (GemvArgs / GemvM1Args<NWT>)
+//   P::act_rsrc, P::act_live      the activations' buffer resource and which of a wave's loads are in range
+//   P::cursor_start, P::load      the stage loader (two-armed load_stage / select-based m1s_load_stage: both were
+//                                 measured separately and both stay)
+// and the wave count NW as a value (blockDim, the argument block's, or the literal 16).
+struct M1General {
+  using Args = GemvArgs;
+  static __device__ __forceinline__ __amdgpu_buffer_rsrc_t act_rsrc(const Args& a, int esz) { return rsrc(a.A, a.K * esz); }
+  static __device__ __forceinline__ bool act_live(const Args& a, int q, int nsl, int k) { return q < nsl && k < a.K; }
+  template <bool ASYM>
+  static __device__ __forceinline__ void cursor_start(const Args& a, StageCursor& c, int v0, int nv, bool idle) {
+    c.s = 0;
+    c.rt = rsrc(a.w[0].tiles, 0);  // zero records: every access out of range (idle waves, past-the-end stages)
+    c.rs = c.rt;
+    c.rz = c.rt;
+    if (!idle && nv > 0) cursor_stripe(a, c, v0);
+  }
+  template <int GPT, bool ASYM, int KSN>
+  static __device__ __forceinline__ void load(const Args& a, StageRegs<GPT, KSN>& S, StageCursor& c, int nv, int nsl,
+                                              int wave, int NW, int v0, int lane, int vs) {
+    load_stage<GPT, ASYM, KSN>(a, S, c, nv, nsl, wave, NW, v0, lane, vs);
+  }
+};
+
+template <class P, int BITS, int GPT, int AT, bool ASYM, int KSN, int SPW, int NST, int ST>
+__device__ __forceinline__ void m1_stream(const typename P::Args& a, int lane, int wave, int NW, int nsl, int v0,
+                                          int nv, bool idle, float* part) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int KT = BITS == 4 ? 128 : 256, SPT = KT / 32, SPG = SPT / GPT;
+  constexpr int KT = k_tile(BITS);
   constexpr int RB = lean_row_bytes(BITS, KSN);  // one fp16 row of a slice
   constexpr int UNITS = KSN * KT / 8;             // 8-element staging units per slice
   constexpr int UPL = UNITS >= 64 ? UNITS / 64 : 1;  // ... per lane (2-tile int4 slices: lanes < 32 hold one)
   constexpr bool PART = UNITS < 64;
-  constexpr int BIAS = BITS == 4 ? 8 : 2;
   constexpr int ESZ = AT == kActF32 ? 4 : 2;
   constexpr bool HL = AT != kActF16;  // fp32 / bf16 rows split into fp16 hi + lo (MFMA rows 0 and 8)
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6));
-  const int NW = __builtin_amdgcn_readfirstlane(int(blockDim.x >> 6));
-  const int nt = a.nt;
-  const int nsl = (nt + KSN - 1) / KSN;
   const bool ulane = !PART || lane < UNITS;  // this lane holds a staging unit of each slice
-  NAD_TRACE(0);
-  if constexpr (BATCH) {
-    const int p = bid / a.batch_wpp;
-    bid -= p * a.batch_wpp;
-    const GemvBatchEnt e = a.batch[p];
-    a.A = e.act;
-    a.w[0].tiles = e.tiles;
-    a.w[0].scales = e.scales;
-    a.w[0].zps = e.zps;
-    a.w[0].out = e.out;
-  }
-  const int u0 = bid * a.u_q + min(bid, a.u_r);
-  const int u1 = u0 + a.u_q + (bid < a.u_r ? 1 : 0);
-  const int vpu = a.dual ? 2 : 1;
-  const int v0 = u0 * vpu, nv = (u1 - u0) * vpu;
-  const bool idle = wave >= nsl;
-  float* part = reinterpret_cast<float*>(smem + a.part_off);  // [nv][16 columns][NW] (NAD_GEMV_LEAN_TAIL), else [nv][NW][16]
 
-  // 1) this wave's activation slices (q = wave + j NW), then the first weight stage
-  const auto ra = rsrc(a.A, a.K * ESZ);
+  // 1) this wave's activation slices (q = wave + j NW; past the end of K the buffer returns zeros), then the first
+  //    weight stage
+  const auto ra = P::act_rsrc(a, ESZ);
   uint4 x[SPW * UPL][2];
 #pragma unroll
   for (int j = 0; j < SPW * UPL; j++) {
     const int q = wave + (j / UPL) * NW, k = q * (KSN * KT) + ((j % UPL) * 64 + lane) * 8;
-    const int off = (ulane && q < nsl && k < a.K) ? k * ESZ : kOOB;
+    const int off = (ulane && P::act_live(a, q, nsl, k)) ? k * ESZ : kOOB;
     x[j][0] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(ra, off, 0, 0));
     if constexpr (ESZ == 4) x[j][1] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(ra, off + 16, 0, 0));
   }
@@ -668,13 +725,9 @@ __device__ __forceinline__ void m1_body(GemvArgs& a, int bid) {
   StageCursor lc;
   lc.j = idle ? nv : 0;
   lc.q = wave;
-  lc.s = 0;
-  lc.rt = rsrc(a.w[0].tiles, 0);
-  lc.rs = lc.rt;
-  lc.rz = lc.rt;
-  if (!idle && nv > 0) cursor_stripe(a, lc, v0);
+  P::template cursor_start<ASYM>(a, lc, v0, nv, idle);
   StageRegs<GPT, KSN> S[NST];
-  load_stage<GPT, ASYM, KSN>(a, S[0], lc, nv, nsl, wave, NW, v0, lane, vs);
+  P::template load<GPT, ASYM, KSN>(a, S[0], lc, nv, nsl, wave, NW, v0, lane, vs);
   NAD_TRACE(4);
 
   // 2) stage the slices into this wave's rows (LDS ops of one wave complete in order: no barrier)
@@ -702,7 +755,7 @@ __device__ __forceinline__ void m1_body(GemvArgs& a, int bid) {
     if constexpr (HL) *reinterpret_cast<h8_t*>(row + RB) = lo;
   }
 #pragma unroll
-  for (int i = 1; i < NST; i++) load_stage<GPT, ASYM, KSN>(a, S[i], lc, nv, nsl, wave, NW, v0, lane, vs);
+  for (int i = 1; i < NST; i++) P::template load<GPT, ASYM, KSN>(a, S[i], lc, nv, nsl, wave, NW, v0, lane, vs);
   NAD_TRACE(1);
 
   // 3) the stream: MFMA row 0 = hi (lane m 0), row 8 = lo (lane m 8), every other row reads the zero row
@@ -711,12 +764,7 @@ __device__ __forceinline__ void m1_body(GemvArgs& a, int bid) {
   const char* abase = wrow + (isrow ? (m == 0 ? RB : 2 * RB) : 0) + kq * 16;
   const int slice_step = isrow ? 2 * RB : 0;
   const int ssh = a.scale_t == kScaleF32 ? 0 : (lane & 1) * 16;
-  Dq4 dq;
-  dq.m0 = __builtin_amdgcn_readfirstlane(a.dq_mask);
-  dq.m1 = dq.m0 << 4;
-  dq.mag = __builtin_amdgcn_readfirstlane(a.dq_magic);
-  dq.s16 = splat(1.f / 16.f);
-  const h2_t zc0 = splat(-(1024.f + BIAS)), zc1 = splat(-(64.f + BIAS));
+  const Dq4 dq = dq4_consts<BITS>(a.dq_mask, a.dq_magic);
 
   f4_t acc = {0.f, 0.f, 0.f, 0.f};
   int cj = idle ? nv : 0, cq = wave, cs = 0;  // compute cursor: local stripe, K-slice, slice ordinal of this wave
@@ -724,33 +772,7 @@ __device__ __forceinline__ void m1_body(GemvArgs& a, int bid) {
   auto compute_stage = [&](const StageRegs<GPT, KSN>& S) {
     if (cj >= nv) return;
     const char* ab = abase + cs * slice_step;
-    f4_t accg[KSN];
-#pragma unroll
-    for (int d = 0; d < SPT; d++) {
-      const int g = GPT == 1 ? 0 : d / SPG;
-#pragma unroll
-      for (int i = 0; i < KSN; i++) {
-        h8_t bf;
-        if constexpr (BITS == 4) {
-          if constexpr (ASYM) {
-            const float z = float(S.zp[i][g]);
-            bf = dequant4(S.b[i][d], dq, zc0 - splat(z), zc1 - splat(z));
-          } else {
-            bf = dequant4(S.b[i][d], dq, zc0, zc1);
-          }
-        } else {
-          bf = BITS == 2 ? dequant2_step(S.b[i], d, BIAS + S.zp[i][g])
-                         : dequant_step<BITS>(S.b[i], d, zp_const(BIAS + S.zp[i][g]));
-        }
-        const h8_t af = *reinterpret_cast<const h8_t*>(ab + i * KT * 2 + d * 64);
-        accg[i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af, bf, d % SPG == 0 ? f4_t{0.f, 0.f, 0.f, 0.f} : accg[i],
-                                                         0, 0, 0);
-      }
-      if ((d + 1) % SPG == 0) {  // group end: scale each tile's group partial into the stripe sum, in tile order
-#pragma unroll
-        for (int i = 0; i < KSN; i++) acc += accg[i] * scale_to_f32<ST>(S.sc[i][g], a.scale_t, ssh);
-      }
-    }
+    stage_mac<BITS, GPT, ASYM, KSN, ST, false>(S, dq, ab, ab, [](int i) { return i * KT * 2; }, a.scale_t, ssh, acc);
     cq += NW;
     cs++;
     if (cq >= nsl) {  // this wave's last slice of stripe cj: publish its partial (row 0 + row 8 = hi + lo)
@@ -758,11 +780,7 @@ __device__ __forceinline__ void m1_body(GemvArgs& a, int bid) {
       if constexpr (HL) {
         r += __shfl_down(r, 32, 64);
       }
-#if NAD_GEMV_LEAN_TAIL
       if (lane < 16) part[(size_t(cj) * 16 + lane) * NW + wave] = r;  // [nv][16 columns][NW]: a column's slots together
-#else
-      if (lane < 16) part[(size_t(cj) * NW + wave) * 16 + lane] = r;
-#endif
       acc = f4_t{0.f, 0.f, 0.f, 0.f};
       cq = wave;
       cs = 0;
@@ -774,11 +792,41 @@ __device__ __forceinline__ void m1_body(GemvArgs& a, int bid) {
 #pragma unroll
     for (int i = 0; i < NST; i++) {
       compute_stage(S[i]);
-      load_stage<GPT, ASYM, KSN>(a, S[i], lc, nv, nsl, wave, NW, v0, lane, vs);
+      P::template load<GPT, ASYM, KSN>(a, S[i], lc, nv, nsl, wave, NW, v0, lane, vs);
     }
   }
   NAD_TRACE_MAX(2);
   __syncthreads();
+}
+
+// woq_gemv_m1_kernel's body: the stream over the full GemvArgs, then the runtime epilogue switch.  A branch-free first
+// weight stage (the two-armed load_stage makes hipcc wait vmcnt(0) for the activation loads before the first weight
+// load) measured neutral (943-947 tok/s) on this kernel and was not kept here; woq_gemv_m1s_kernel below, which serves
+// the decode token's launches, has no control flow around any stage's loads.
+template <int BITS, int GPT, int AT, bool ASYM, int KSN, int SPW, bool BATCH, int NST, int ST = -1>
+__device__ __forceinline__ void m1_body(GemvArgs& a, int bid) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6));
+  const int NW = __builtin_amdgcn_readfirstlane(int(blockDim.x >> 6));
+  const int nsl = (a.nt + KSN - 1) / KSN;
+  NAD_TRACE(0);
+  if constexpr (BATCH) {
+    const int p = bid / a.batch_wpp;
+    bid -= p * a.batch_wpp;
+    const GemvBatchEnt e = a.batch[p];
+    a.A = e.act;
+    a.w[0].tiles = e.tiles;
+    a.w[0].scales = e.scales;
+    a.w[0].zps = e.zps;
+    a.w[0].out = e.out;
+  }
+  const int u0 = bid * a.u_q + min(bid, a.u_r);
+  const int u1 = u0 + a.u_q + (bid < a.u_r ? 1 : 0);
+  const int vpu = a.dual ? 2 : 1;
+  const int v0 = u0 * vpu, nv = (u1 - u0) * vpu;
+  float* part = reinterpret_cast<float*>(smem + a.part_off);  // [nv][16 columns][NW]
+  m1_stream<M1General, BITS, GPT, AT, ASYM, KSN, SPW, NST, ST>(a, lane, wave, NW, nsl, v0, nv, wave >= nsl, part);
 
   // 4) sum each stripe's wave slots in wave order and apply the epilogue
   const int nout = (u1 - u0) * 16;
@@ -825,61 +873,24 @@ __device__ __forceinline__ void m1_body(GemvArgs& a, int bid) {
     }
     out[n] = v;
   };
-#if NAD_GEMV_LEAN_TAIL
-  if (nwl == 16 && NW == 16) {  // 16 waves with a slice each: four 16-B reads per column, no clamps or masks
+  if (nwl == 16 && NW == 16) {  // 16 waves with a slice each
     for (int o = threadIdx.x; o < nout; o += blockDim.x) {
       const int p = o >> 4, nn = o & 15;
       float y[2] = {0.f, 0.f};
 #pragma unroll
-      for (int h = 0; h < 2; h++) {
-        if (h < vpu) {
-          const float4* ps = reinterpret_cast<const float4*>(part + (size_t(p * vpu + h) * 16 + nn) * 16);
-          const float4 t0 = ps[0], t1 = ps[1], t2 = ps[2], t3 = ps[3];
-          // the general order below at nwl = 16: s_i sums slots i, i + 4, i + 8, i + 12
-          const float s0 = ((t0.x + t1.x) + t2.x) + t3.x, s1 = ((t0.y + t1.y) + t2.y) + t3.y;
-          const float s2 = ((t0.z + t1.z) + t2.z) + t3.z, s3 = ((t0.w + t1.w) + t2.w) + t3.w;
-          y[h] = (s0 + s1) + (s2 + s3);
-        }
-      }
+      for (int h = 0; h < 2; h++)
+        if (h < vpu) y[h] = reduce16(part + (size_t(p * vpu + h) * 16 + nn) * 16);
       emit(p, nn, y);
     }
     NAD_TRACE(3);
     return;
   }
-#endif
   for (int o = threadIdx.x; o < nout; o += blockDim.x) {
     const int p = o >> 4, nn = o & 15;
     float y[2] = {0.f, 0.f};
 #pragma unroll
-    for (int h = 0; h < 2; h++) {
-      if (h < vpu) {  // all slots read at once (one LDS round trip), summed in the general kernel's order
-#if NAD_GEMV_LEAN_TAIL
-        const float* ps = part + (size_t(p * vpu + h) * 16 + nn) * NW;
-#define NAD_SLOT(w) ps[w]
-#else
-        const float* ps = part + size_t(p * vpu + h) * NW * 16 + nn;
-#define NAD_SLOT(w) ps[(w) * 16]
-#endif
-        float t[16];
-#pragma unroll
-        for (int w = 0; w < 16; w++) t[w] = NAD_SLOT(min(w, nwl - 1));
-#undef NAD_SLOT
-        const int full = nwl & ~3;
-        float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-#pragma unroll
-        for (int w = 0; w < 16; w += 4)
-          if (w < full) {
-            s0 += t[w];
-            s1 += t[w + 1];
-            s2 += t[w + 2];
-            s3 += t[w + 3];
-          }
-#pragma unroll
-        for (int w = 0; w < 16; w++)
-          if (w >= full && w < nwl) s0 += t[w];
-        y[h] = (s0 + s1) + (s2 + s3);
-      }
-    }
+    for (int h = 0; h < 2; h++)
+      if (h < vpu) y[h] = reduce_slots(part + (size_t(p * vpu + h) * 16 + nn) * NW, nwl);
     emit(p, nn, y);
   }
   NAD_TRACE(3);
@@ -965,26 +976,7 @@ template <int GPT, bool ASYM, int KSN, int NWT>
 __device__ __forceinline__ void m1s_load_stage(const GemvM1Args<NWT>& a, StageRegs<GPT, KSN>& S, StageCursor& c, int nv,
                                                int nsl, int wave, int NW, int v0, int lane, int vs) {
   const bool on = c.j < nv;
-  const int nt = a.nt, ng = a.ng;
-  const int t0 = c.q * KSN;
-  const int tb = (c.s * nt + t0) * 1024;
-  const int rowb = a.scale_t == kScaleF32 ? 64 : 32;  // bytes per scale row of 16
-#pragma unroll
-  for (int i = 0; i < KSN; i++) {
-    const bool live = on && t0 + i < nt;
-    S.b[i] = __builtin_bit_cast(u4_t, __builtin_amdgcn_raw_buffer_load_b128(c.rt, (live ? tb + i * 1024 : kOOB) + lane * 16, 0, NAD_TILE_AUX));
-#pragma unroll
-    for (int g = 0; g < GPT; g++) {
-      const int grp = GPT == 1 ? ((t0 + i) >> a.tpg_shift) : (t0 + i) * GPT + g;
-      const bool gl = live && (GPT == 1 || grp < ng);
-      const int row = c.s * ng + grp;
-      S.sc[i][g] = __builtin_amdgcn_raw_buffer_load_b32(c.rs, (gl ? row * rowb : kOOB) + vs, 0, 0);
-      if constexpr (ASYM)
-        S.zp[i][g] = int(int8_t(__builtin_amdgcn_raw_buffer_load_b8(c.rz, (gl ? row * 16 : kOOB) + (lane & 15), 0, 0)));
-      else
-        S.zp[i][g] = 0;
-    }
-  }
+  stage_loads<ASYM>(a, S, c, on, lane, vs);
   if (on) {
     c.q += NW;
     if (c.q >= nsl) {
@@ -995,24 +987,31 @@ __device__ __forceinline__ void m1s_load_stage(const GemvM1Args<NWT>& a, StageRe
   }
 }
 
+template <int NWT>
+struct M1Spec {  // m1_stream's policy for woq_gemv_m1s_kernel
+  using Args = GemvM1Args<NWT>;
+  static __device__ __forceinline__ __amdgpu_buffer_rsrc_t act_rsrc(const Args& a, int) { return rsrc(a.A, a.a_bytes); }
+  static __device__ __forceinline__ bool act_live(const Args&, int, int, int) { return true; }
+  template <bool ASYM>
+  static __device__ __forceinline__ void cursor_start(const Args& a, StageCursor& c, int v0, int nv, bool) {
+    m1s_cursor_stripe<NWT, ASYM>(a, c, v0, c.j < nv);
+  }
+  template <int GPT, bool ASYM, int KSN>
+  static __device__ __forceinline__ void load(const Args& a, StageRegs<GPT, KSN>& S, StageCursor& c, int nv, int nsl,
+                                              int wave, int NW, int v0, int lane, int vs) {
+    m1s_load_stage<GPT, ASYM, KSN, NWT>(a, S, c, nv, nsl, wave, NW, v0, lane, vs);
+  }
+};
+
 template <int BITS, int GPT, int AT, bool ASYM, int KSN, int SPW, int NST, int ST, int NWT, bool L16>
 __global__ __launch_bounds__((m1_max_threads<GPT, KSN>())) void woq_gemv_m1s_kernel(GemvM1Args<NWT> a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   static_assert(NWT >= 1 && NWT <= 3, "1 weight, the {gate, up} pair, or 3 weights");
-  constexpr int KT = BITS == 4 ? 128 : 256, SPT = KT / 32, SPG = SPT / GPT;
-  constexpr int RB = lean_row_bytes(BITS, KSN);  // one fp16 row of a slice
-  constexpr int UNITS = KSN * KT / 8;             // 8-element staging units per slice
-  constexpr int UPL = UNITS >= 64 ? UNITS / 64 : 1;  // ... per lane (2-tile int4 slices: lanes < 32 hold one)
-  constexpr bool PART = UNITS < 64;
-  constexpr int BIAS = BITS == 4 ? 8 : 2;
-  constexpr int ESZ = AT == kActF32 ? 4 : 2;
-  constexpr bool HL = AT != kActF16;  // fp32 / bf16 rows split into fp16 hi + lo (MFMA rows 0 and 8)
   constexpr int VPU = NWT == 2 ? 2 : 1;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6));
   const int NW = L16 ? 16 : a.nw;
   const int nsl = a.nsl;
-  const bool ulane = !PART || lane < UNITS;  // this lane holds a staging unit of each slice
   NAD_TRACE(0);
   const int bid = int(blockIdx.x);
   const int u0 = bid * a.u_q + min(bid, a.u_r);
@@ -1020,125 +1019,7 @@ __global__ __launch_bounds__((m1_max_threads<GPT, KSN>())) void woq_gemv_m1s_ker
   const int v0 = u0 * VPU, nv = nu * VPU;
   const bool idle = !L16 && wave >= nsl;  // L16: every wave owns a slice
   float* part = reinterpret_cast<float*>(smem + a.part_off);  // [nv][16 columns][NW]
-
-  // 1) this wave's activation slices (q = wave + j NW; past the end of K the buffer returns zeros), then the first
-  //    weight stage
-  const auto ra = rsrc(a.A, a.a_bytes);
-  uint4 x[SPW * UPL][2];
-#pragma unroll
-  for (int j = 0; j < SPW * UPL; j++) {
-    const int q = wave + (j / UPL) * NW, k = q * (KSN * KT) + ((j % UPL) * 64 + lane) * 8;
-    const int off = ulane ? k * ESZ : kOOB;
-    x[j][0] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(ra, off, 0, 0));
-    if constexpr (ESZ == 4) x[j][1] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(ra, off + 16, 0, 0));
-  }
-  const int vs = a.scale_t == kScaleF32 ? (lane & 15) * 4 : (lane & 14) * 2;
-  StageCursor lc;
-  lc.j = idle ? nv : 0;
-  lc.q = wave;
-  m1s_cursor_stripe<NWT, ASYM>(a, lc, v0, lc.j < nv);
-  StageRegs<GPT, KSN> S[NST];
-  m1s_load_stage<GPT, ASYM, KSN, NWT>(a, S[0], lc, nv, nsl, wave, NW, v0, lane, vs);
-  NAD_TRACE(4);
-
-  // 2) stage the slices into this wave's rows (LDS ops of one wave complete in order: no barrier)
-  char* wrow = smem + wave * lean_wave_lds(BITS, KSN, SPW);
-#pragma unroll
-  for (int u = 0; u < UPL; u++)
-    if (ulane) *reinterpret_cast<uint4*>(wrow + (u * 64 + lane) * 16) = make_uint4(0u, 0u, 0u, 0u);
-#pragma unroll
-  for (int j = 0; j < SPW * UPL; j++) {
-    if (!ulane) break;
-    h8_t hi, lo;
-    if constexpr (AT == kActF16) {
-      hi = __builtin_bit_cast(h8_t, x[j][0]);
-    } else {
-      float f[8];
-      unit_to_f32(AT, x[j][0], x[j][1], f);
-#pragma unroll
-      for (int e = 0; e < 8; e++) {
-        hi[e] = _Float16(f[e]);
-        lo[e] = _Float16(f[e] - float(hi[e]));
-      }
-    }
-    char* row = wrow + RB + (j / UPL) * 2 * RB + ((j % UPL) * 64 + lane) * 16;
-    *reinterpret_cast<h8_t*>(row) = hi;
-    if constexpr (HL) *reinterpret_cast<h8_t*>(row + RB) = lo;
-  }
-#pragma unroll
-  for (int i = 1; i < NST; i++) m1s_load_stage<GPT, ASYM, KSN, NWT>(a, S[i], lc, nv, nsl, wave, NW, v0, lane, vs);
-  NAD_TRACE(1);
-
-  // 3) the stream: MFMA row 0 = hi (lane m 0), row 8 = lo (lane m 8), every other row reads the zero row
-  const int m = lane & 15, kq = lane >> 4;
-  const bool isrow = m == 0 || (HL && m == 8);
-  const char* abase = wrow + (isrow ? (m == 0 ? RB : 2 * RB) : 0) + kq * 16;
-  const int slice_step = isrow ? 2 * RB : 0;
-  const int ssh = a.scale_t == kScaleF32 ? 0 : (lane & 1) * 16;
-  Dq4 dq;
-  dq.m0 = __builtin_amdgcn_readfirstlane(a.dq_mask);
-  dq.m1 = dq.m0 << 4;
-  dq.mag = __builtin_amdgcn_readfirstlane(a.dq_magic);
-  dq.s16 = splat(1.f / 16.f);
-  const h2_t zc0 = splat(-(1024.f + BIAS)), zc1 = splat(-(64.f + BIAS));
-
-  f4_t acc = {0.f, 0.f, 0.f, 0.f};
-  int cj = idle ? nv : 0, cq = wave, cs = 0;  // compute cursor: local stripe, K-slice, slice ordinal of this wave
-
-  auto compute_stage = [&](const StageRegs<GPT, KSN>& S) {
-    if (cj >= nv) return;
-    const char* ab = abase + cs * slice_step;
-    f4_t accg[KSN];
-#pragma unroll
-    for (int d = 0; d < SPT; d++) {
-      const int g = GPT == 1 ? 0 : d / SPG;
-#pragma unroll
-      for (int i = 0; i < KSN; i++) {
-        h8_t bf;
-        if constexpr (BITS == 4) {
-          if constexpr (ASYM) {
-            const float z = float(S.zp[i][g]);
-            bf = dequant4(S.b[i][d], dq, zc0 - splat(z), zc1 - splat(z));
-          } else {
-            bf = dequant4(S.b[i][d], dq, zc0, zc1);
-          }
-        } else {
-          bf = BITS == 2 ? dequant2_step(S.b[i], d, BIAS + S.zp[i][g])
-                         : dequant_step<BITS>(S.b[i], d, zp_const(BIAS + S.zp[i][g]));
-        }
-        const h8_t af = *reinterpret_cast<const h8_t*>(ab + i * KT * 2 + d * 64);
-        accg[i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af, bf, d % SPG == 0 ? f4_t{0.f, 0.f, 0.f, 0.f} : accg[i],
-                                                         0, 0, 0);
-      }
-      if ((d + 1) % SPG == 0) {  // group end: scale each tile's group partial into the stripe sum, in tile order
-#pragma unroll
-        for (int i = 0; i < KSN; i++) acc += accg[i] * scale_to_f32<ST>(S.sc[i][g], a.scale_t, ssh);
-      }
-    }
-    cq += NW;
-    cs++;
-    if (cq >= nsl) {  // this wave's last slice of stripe cj: publish its partial (row 0 + row 8 = hi + lo)
-      float r = acc[0];
-      if constexpr (HL) {
-        r += __shfl_down(r, 32, 64);
-      }
-      if (lane < 16) part[(size_t(cj) * 16 + lane) * NW + wave] = r;  // a column's slots together
-      acc = f4_t{0.f, 0.f, 0.f, 0.f};
-      cq = wave;
-      cs = 0;
-      cj++;
-    }
-  };
-
-  while (cj < nv) {
-#pragma unroll
-    for (int i = 0; i < NST; i++) {
-      compute_stage(S[i]);
-      m1s_load_stage<GPT, ASYM, KSN, NWT>(a, S[i], lc, nv, nsl, wave, NW, v0, lane, vs);
-    }
-  }
-  NAD_TRACE_MAX(2);
-  __syncthreads();
+  m1_stream<M1Spec<NWT>, BITS, GPT, AT, ASYM, KSN, SPW, NST, ST>(a, lane, wave, NW, nsl, v0, nv, idle, part);
 
   // 4) sum each stripe's wave slots in wave order (m1_body's order exactly), then the store
   const int nout = nu * 16;
@@ -1147,34 +1028,10 @@ __global__ __launch_bounds__((m1_max_threads<GPT, KSN>())) void woq_gemv_m1s_ker
     float y[VPU];
 #pragma unroll
     for (int h = 0; h < VPU; h++) {
-      if constexpr (L16) {  // four 16-B reads per column, no clamps or masks
-        const float4* ps = reinterpret_cast<const float4*>(part + (size_t(p * VPU + h) * 16 + nn) * 16);
-        const float4 t0 = ps[0], t1 = ps[1], t2 = ps[2], t3 = ps[3];
-        // s_i sums slots i, i + 4, i + 8, i + 12
-        const float s0 = ((t0.x + t1.x) + t2.x) + t3.x, s1 = ((t0.y + t1.y) + t2.y) + t3.y;
-        const float s2 = ((t0.z + t1.z) + t2.z) + t3.z, s3 = ((t0.w + t1.w) + t2.w) + t3.w;
-        y[h] = (s0 + s1) + (s2 + s3);
-      } else {  // all slots read at once (one LDS round trip)
-        const int nwl = min(NW, nsl);
-        const float* ps = part + (size_t(p * VPU + h) * 16 + nn) * NW;
-        float t[16];
-#pragma unroll
-        for (int w = 0; w < 16; w++) t[w] = ps[min(w, nwl - 1)];
-        const int full = nwl & ~3;
-        float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-#pragma unroll
-        for (int w = 0; w < 16; w += 4)
-          if (w < full) {
-            s0 += t[w];
-            s1 += t[w + 1];
-            s2 += t[w + 2];
-            s3 += t[w + 3];
-          }
-#pragma unroll
-        for (int w = 0; w < 16; w++)
-          if (w >= full && w < nwl) s0 += t[w];
-        y[h] = (s0 + s1) + (s2 + s3);
-      }
+      if constexpr (L16)
+        y[h] = reduce16(part + (size_t(p * VPU + h) * 16 + nn) * 16);
+      else
+        y[h] = reduce_slots(part + (size_t(p * VPU + h) * 16 + nn) * NW, min(NW, nsl));
     }
     const M1Sel<NWT> vsel(a, v0 + p * VPU);
     const int wsel = NWT == 2 ? 0 : vsel.w;
@@ -1193,65 +1050,62 @@ __global__ __launch_bounds__((m1_max_threads<GPT, KSN>())) void woq_gemv_m1s_ker
 }
 
 // ------------------------------------------------------------------------------------------------ launcher
-template <int BITS, int HILO, int GPT, bool ASYM, int NST>
-static hipError_t gemv_launch5(const GemvArgs& a, dim3 g, dim3 b, size_t lds, hipStream_t st) {
-  auto k = woq_gemv_kernel<BITS, HILO, GPT, ASYM, NST>;
-  static bool attr_set = false;  // opt in to > 64 KiB of dynamic LDS once per instantiation
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       160 * 1024);
-    if (e != hipSuccess) return e;
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(k, g, b, lds, st, a);
-  return hipGetLastError();
-}
-template <int BITS, int HILO, int GPT, bool ASYM>
-static hipError_t gemv_launch4(const GemvArgs& a, dim3 g, dim3 b, size_t lds, hipStream_t st) {
-  // stages of the busiest wave: its (stripe, KS-tile slice) pairs
-  const int nsl = (a.nt + KS - 1) / KS, waves = int(b.x / 64);
-  const int spw = (a.u_q + (a.u_r ? 1 : 0)) * (a.dual ? 2 : 1) * ((nsl + waves - 1) / waves);
-  const int nst = a.m1_nst == 1 ? 1 : (a.m1_nst == 3 ? 3 : (spw <= 2 ? 1 : 3));
-  return nst == 1 ? gemv_launch5<BITS, HILO, GPT, ASYM, 1>(a, g, b, lds, st)
-                  : gemv_launch5<BITS, HILO, GPT, ASYM, 3>(a, g, b, lds, st);
-}
-
-template <int BITS, int GPT, int AT, bool ASYM, int KSN, int SPW, int NST, int ST>
-static hipError_t gemv_m1_launch6(const GemvArgs& a, dim3 g, dim3 b, size_t lds, hipStream_t st) {
-  auto k = woq_gemv_m1_kernel<BITS, GPT, AT, ASYM, KSN, SPW, false, NST, ST>;
+// Opt kernel K in to > 64 KiB of dynamic LDS once (the flag is K's own: one instance of this template per kernel
+// instantiation), then launch it.
+template <auto K, class... Args>
+static hipError_t launch_big_lds(dim3 g, dim3 b, size_t lds, hipStream_t st, const Args&... args) {
   static bool attr_set = false;
   if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize,
                                        160 * 1024);
     if (e != hipSuccess) return e;
     attr_set = true;
   }
-  hipLaunchKernelGGL(k, g, b, lds, st, a);
+  hipLaunchKernelGGL(K, g, b, lds, st, args...);
   return hipGetLastError();
 }
-// register stages per wave of a single-problem launch: the most (stripe, K-slice) stages any wave streams
+
+// the most (stripe, K-slice) stages any wave of a single-problem launch streams
 static int m1_stages_per_wave(const GemvArgs& a, int ksn, int waves) {
   const int nsl = (a.nt + ksn - 1) / ksn;
   return (a.u_q + (a.u_r ? 1 : 0)) * (a.dual ? 2 : 1) * ((nsl + waves - 1) / waves);
 }
+// register stages per wave of an M = 1 launch (NST of m1_body: the measurements are there); NAD_GEMV_NST overrides
+static int m1_nst(const GemvArgs& a, int ksn, int waves) {
+  if (a.m1_nst == 1 || a.m1_nst == 2) return a.m1_nst;
+  const int spw = m1_stages_per_wave(a, ksn, waves);
+  return spw >= 7 || (ksn == 1 && spw >= 4) ? 2 : 1;
+}
+
+// the launch's runtime activation type / symmetry as the compile-time argument of f
+template <int V>
+using IntC = std::integral_constant<int, V>;
+template <class F>
+static auto by_act(const GemvArgs& a, F f) {
+  if (a.act_t == kActF32) return f(IntC<kActF32>{});
+  if (a.act_t == kActF16) return f(IntC<kActF16>{});
+  return f(IntC<kActBF16>{});
+}
+template <class F>
+static auto by_asym(const GemvArgs& a, F f) {
+  return a.asym ? f(std::true_type{}) : f(std::false_type{});
+}
+
+template <int BITS, int HILO, int GPT, bool ASYM>
+static hipError_t gemv_launch4(const GemvArgs& a, dim3 g, dim3 b, size_t lds, hipStream_t st) {
+  const int spw = m1_stages_per_wave(a, KS, int(b.x / 64));
+  const int nst = a.m1_nst == 1 ? 1 : (a.m1_nst == 3 ? 3 : (spw <= 2 ? 1 : 3));
+  return nst == 1 ? launch_big_lds<woq_gemv_kernel<BITS, HILO, GPT, ASYM, 1>>(g, b, lds, st, a)
+                  : launch_big_lds<woq_gemv_kernel<BITS, HILO, GPT, ASYM, 3>>(g, b, lds, st, a);
+}
+
 template <int BITS, int GPT, int AT, bool ASYM, int KSN, int SPW, int ST>
 static hipError_t gemv_m1_launch5(const GemvArgs& a, dim3 g, dim3 b, size_t lds, hipStream_t st) {
-  if (a.batch) {
-    auto kb = woq_gemv_m1_kernel<BITS, GPT, AT, ASYM, KSN, SPW, true, NAD_M1_BATCH_NST, ST>;
-    static bool attr_b = false;
-    if (!attr_b) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kb), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         160 * 1024);
-      if (e != hipSuccess) return e;
-      attr_b = true;
-    }
-    hipLaunchKernelGGL(kb, g, b, lds, st, a);
-    return hipGetLastError();
-  }
-  const int spw = m1_stages_per_wave(a, KSN, int(b.x / 64));
-  const int nst = a.m1_nst == 1 || a.m1_nst == 2 ? a.m1_nst : (spw >= 7 || (KSN == 1 && spw >= 4) ? 2 : 1);
-  return nst == 1 ? gemv_m1_launch6<BITS, GPT, AT, ASYM, KSN, SPW, 1, ST>(a, g, b, lds, st)
-                  : gemv_m1_launch6<BITS, GPT, AT, ASYM, KSN, SPW, 2, ST>(a, g, b, lds, st);
+  if (a.batch)
+    return launch_big_lds<woq_gemv_m1_kernel<BITS, GPT, AT, ASYM, KSN, SPW, true, NAD_M1_BATCH_NST, ST>>(g, b, lds, st, a);
+  return m1_nst(a, KSN, int(b.x / 64)) == 1
+             ? launch_big_lds<woq_gemv_m1_kernel<BITS, GPT, AT, ASYM, KSN, SPW, false, 1, ST>>(g, b, lds, st, a)
+             : launch_big_lds<woq_gemv_m1_kernel<BITS, GPT, AT, ASYM, KSN, SPW, false, 2, ST>>(g, b, lds, st, a);
 }
 // int2: the scale type as a template parameter (3 x the int2 instantiations; int4 keeps the runtime form)
 #ifndef NAD_INT2_ST
@@ -1309,17 +1163,8 @@ static GemvM1Args<NWT> m1s_args(const GemvArgs& a, int ksn, int waves) {
 }
 template <int BITS, int GPT, int AT, bool ASYM, int KSN, int SPW, int NST, int ST, int NWT, bool L16>
 static hipError_t m1s_go(const GemvArgs& a, dim3 g, dim3 b, size_t lds, hipStream_t st) {
-  auto k = woq_gemv_m1s_kernel<BITS, GPT, AT, ASYM, KSN, SPW, NST, ST, NWT, L16>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       160 * 1024);
-    if (e != hipSuccess) return e;
-    attr_set = true;
-  }
-  const GemvM1Args<NWT> c = m1s_args<NWT>(a, KSN, int(b.x / 64));
-  hipLaunchKernelGGL(k, g, b, lds, st, c);
-  return hipGetLastError();
+  return launch_big_lds<woq_gemv_m1s_kernel<BITS, GPT, AT, ASYM, KSN, SPW, NST, ST, NWT, L16>>(
+      g, b, lds, st, m1s_args<NWT>(a, KSN, int(b.x / 64)));
 }
 // weights of the launch as woq_gemv_m1s_kernel's NWT (0: not served)
 static int m1s_nwt(const GemvArgs& a) {
@@ -1338,8 +1183,7 @@ static bool m1s_launch3(const GemvArgs& a, dim3 g, dim3 b, size_t lds, hipStream
   if (nwt == 0) return false;
   const int nsl = (a.nt + ks - 1) / ks;
   const bool l16 = waves == 16 && nsl >= 16;
-  const int spw = m1_stages_per_wave(a, ks, waves);
-  const int nst = a.m1_nst == 1 || a.m1_nst == 2 ? a.m1_nst : (spw >= 7 || (ks == 1 && spw >= 4) ? 2 : 1);
+  const int nst = m1_nst(a, ks, waves);
 #define NAD_M1S(KSN, SPW, NST, NWT, L16)                                                         \
   do {                                                                                           \
     if (e) *e = m1s_go<BITS, GPT, AT, ASYM, KSN, SPW, NST, ST, NWT, L16>(a, g, b, lds, st);      \
@@ -1380,17 +1224,12 @@ static bool m1s_launch3(const GemvArgs& a, dim3 g, dim3 b, size_t lds, hipStream
 #if !defined(GEMV_PART) || GEMV_PART == 2
 // int4: every activation type at one group per tile, fp32 activations at two
 bool gemv_m1s_launch_b4(const GemvArgs& a, int gpt, dim3 g, dim3 b, size_t lds, hipStream_t st, hipError_t* e) {
-  if (gpt == 1) {
-    if (a.act_t == kActF32) return a.asym ? m1s_launch3<4, 1, kActF32, true, -1>(a, g, b, lds, st, e)
-                                          : m1s_launch3<4, 1, kActF32, false, -1>(a, g, b, lds, st, e);
-    if (a.act_t == kActF16) return a.asym ? m1s_launch3<4, 1, kActF16, true, -1>(a, g, b, lds, st, e)
-                                          : m1s_launch3<4, 1, kActF16, false, -1>(a, g, b, lds, st, e);
-    return a.asym ? m1s_launch3<4, 1, kActBF16, true, -1>(a, g, b, lds, st, e)
-                  : m1s_launch3<4, 1, kActBF16, false, -1>(a, g, b, lds, st, e);
-  }
+  if (gpt == 1)
+    return by_act(a, [&](auto at) {
+      return by_asym(a, [&](auto as) { return m1s_launch3<4, 1, at.value, as.value, -1>(a, g, b, lds, st, e); });
+    });
   if (gpt == 2 && a.act_t == kActF32)
-    return a.asym ? m1s_launch3<4, 2, kActF32, true, -1>(a, g, b, lds, st, e)
-                  : m1s_launch3<4, 2, kActF32, false, -1>(a, g, b, lds, st, e);
+    return by_asym(a, [&](auto as) { return m1s_launch3<4, 2, kActF32, as.value, -1>(a, g, b, lds, st, e); });
   return false;
 }
 #else
@@ -1417,12 +1256,9 @@ bool gemv_m1s_launch_b2(const GemvArgs& a, int gpt, dim3 g, dim3 b, size_t lds, 
 
 template <int BITS, int GPT>
 static hipError_t gemv_m1_launch2(const GemvArgs& a, dim3 g, dim3 b, size_t lds, hipStream_t st) {
-  if (a.act_t == kActF32) return a.asym ? gemv_m1_launch4<BITS, GPT, kActF32, true>(a, g, b, lds, st)
-                                        : gemv_m1_launch4<BITS, GPT, kActF32, false>(a, g, b, lds, st);
-  if (a.act_t == kActF16) return a.asym ? gemv_m1_launch4<BITS, GPT, kActF16, true>(a, g, b, lds, st)
-                                        : gemv_m1_launch4<BITS, GPT, kActF16, false>(a, g, b, lds, st);
-  return a.asym ? gemv_m1_launch4<BITS, GPT, kActBF16, true>(a, g, b, lds, st)
-                : gemv_m1_launch4<BITS, GPT, kActBF16, false>(a, g, b, lds, st);
+  return by_act(a, [&](auto at) {
+    return by_asym(a, [&](auto as) { return gemv_m1_launch4<BITS, GPT, at.value, as.value>(a, g, b, lds, st); });
+  });
 }
 // int4 / int2 with one group per tile or 2 per tile; int2 also 4 per tile (sym only, as the general kernel).  The
 // int2 instantiations (3 scale types each) compile as their own object (woq_gemv_b2.o: GEMV_PART=1) in parallel with
@@ -1431,9 +1267,8 @@ static hipError_t gemv_m1_launch2(const GemvArgs& a, dim3 g, dim3 b, size_t lds,
 hipError_t gemv_m1_launch_b2(const GemvArgs& a, int gpt, dim3 g, dim3 b, size_t lds, hipStream_t st) {
   if (gpt == 1) return gemv_m1_launch2<2, 1>(a, g, b, lds, st);
   if (gpt == 2) return gemv_m1_launch2<2, 2>(a, g, b, lds, st);
-  if (gpt == 4 && !a.asym) return a.act_t == kActF32 ? gemv_m1_launch4<2, 4, kActF32, false>(a, g, b, lds, st)
-                                 : (a.act_t == kActF16 ? gemv_m1_launch4<2, 4, kActF16, false>(a, g, b, lds, st)
-                                                       : gemv_m1_launch4<2, 4, kActBF16, false>(a, g, b, lds, st));
+  if (gpt == 4 && !a.asym)
+    return by_act(a, [&](auto at) { return gemv_m1_launch4<2, 4, at.value, false>(a, g, b, lds, st); });
   return hipErrorInvalidValue;
 }
 #else
@@ -1453,17 +1288,15 @@ static hipError_t gemv_m1_launch(const GemvArgs& a, int bits, int gpt, dim3 g, d
 // woq_skinny_kernel.
 template <int BITS, int HILO>
 static hipError_t gemv_launch2(const GemvArgs& a, int gpt, dim3 g, dim3 b, size_t lds, hipStream_t st) {
-  constexpr int SPT = (BITS == 4 ? 128 : (BITS == 2 ? 256 : 64)) / 32;
-  if (gpt == 1) return a.asym ? gemv_launch4<BITS, HILO, 1, true>(a, g, b, lds, st)
-                              : gemv_launch4<BITS, HILO, 1, false>(a, g, b, lds, st);
-  if (gpt == 2) return a.asym ? gemv_launch4<BITS, HILO, 2, true>(a, g, b, lds, st)
-                              : gemv_launch4<BITS, HILO, 2, false>(a, g, b, lds, st);
-  if constexpr (SPT % 4 == 0) {
-    if (gpt == 4)
-      return a.asym ? gemv_launch4<BITS, HILO, 4, true>(a, g, b, lds, st)
-                    : gemv_launch4<BITS, HILO, 4, false>(a, g, b, lds, st);
-  }
-  return hipErrorInvalidValue;
+  constexpr int SPT = k_tile(BITS) / 32;
+  return by_asym(a, [&](auto as) {
+    if (gpt == 1) return gemv_launch4<BITS, HILO, 1, as.value>(a, g, b, lds, st);
+    if (gpt == 2) return gemv_launch4<BITS, HILO, 2, as.value>(a, g, b, lds, st);
+    if constexpr (SPT % 4 == 0) {
+      if (gpt == 4) return gemv_launch4<BITS, HILO, 4, as.value>(a, g, b, lds, st);
+    }
+    return hipError_t(hipErrorInvalidValue);
+  });
 }
 
 template <int BITS>
@@ -1566,19 +1399,10 @@ hipError_t launch_gemv_dual(const GemvArgs& a, const GemvArgs& b, int ga, int gb
                             hipStream_t stream) {
   int tpg = 0;
   const int g1 = gemv_groups_per_tile(2, a.nt, a.ng, a.bs, &tpg);
-  auto go = [&](auto k) -> hipError_t {
-    static bool attr = false;
-    if (!attr) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         160 * 1024);
-      if (e != hipSuccess) return e;
-      attr = true;
-    }
-    hipLaunchKernelGGL(k, dim3(ga + gb), dim3(waves * 64), lds, stream, a, b, ga);
-    return hipGetLastError();
-  };
-  if (g1 == 4) return go(woq_gemv_m1_dual_kernel<2, 4, 1, 4, 2, 2, kActF32>);  // groups of 64
-  return go(woq_gemv_m1_dual_kernel<2, 2, 1, 4, 1, 2, kActF32>);              // groups of 128
+  const dim3 g(ga + gb), blk(waves * 64);
+  if (g1 == 4)  // groups of 64
+    return launch_big_lds<woq_gemv_m1_dual_kernel<2, 4, 1, 4, 2, 2, kActF32>>(g, blk, lds, stream, a, b, ga);
+  return launch_big_lds<woq_gemv_m1_dual_kernel<2, 2, 1, 4, 1, 2, kActF32>>(g, blk, lds, stream, a, b, ga);  // of 128
 }
 
 hipError_t launch_gemv_batch(const GemvArgs& a, int bits, int waves, int grid, size_t lds, hipStream_t stream) {

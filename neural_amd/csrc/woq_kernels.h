@@ -119,10 +119,9 @@ struct GemvArgs {
   int act_t;            // ActType
   int dual;             // units are {w[0] stripe s, w[1] stripe s} pairs (SiLU*mul / GELU*mul)
   int units;            // stripes (non-dual, summed over the weights) or stripe pairs (dual)
-  int stripe_base[4];   // non-dual: first virtual stripe of each weight (unused entries = INT_MAX)
+  int stripe_base[3];   // non-dual: first virtual stripe of each weight (unused entries = INT_MAX)
   int nt, ng, bs;       // tiles along K, groups along K, group size
-  int tpg_mask;         // GPT == 1: tiles per group - 1 (power of two; 0x7fffffff for one group), group = t >> shift
-  int tpg_shift;
+  int tpg_shift;        // GPT == 1: log2(tiles per group) (a power of two; 31 for one group), group = t >> shift
   int scale_t;
   int asym;
   int epi;
@@ -135,10 +134,6 @@ struct GemvArgs {
   int part_off;         // LDS byte offset of the partial-sum slots
   uint32_t dq_mask;     // 0x000F000F and 0x64006400: int4 dequant constants, passed in so they stay in registers
   uint32_t dq_magic;
-  int nwa;              // woq_chain: waves that own K slices in this op (the single-op launch's wave count)
-  int norm;             // woq_chain: RMS-normalise each activation row while staging (x / rms(x) * norm_w)
-  float norm_eps;
-  const float* norm_w;  //   optional per-k weight (null = 1)
   int u_q, u_r;         // units per workgroup: u_q, one more for the first u_r workgroups (host-divided)
   int lean;             // M = 1 int4 single-group-per-tile launches may take woq_gemv_m1_kernel (NAD_GEMV_LEAN)
   int lean_ks;          // woq_gemv_m1_kernel: K tiles per K-slice (4, or 1 / 2 where that gives each of up to 16 waves one)
@@ -152,8 +147,8 @@ struct GemvArgs {
 
 // The argument block of woq_gemv_m1s_kernel: only what that kernel reads, in the order it reads it, with everything
 // that is constant per launch worked out by launch_gemv (buffer sizes, K-slices per stripe, units per workgroup).  A
-// one-weight launch is 128 bytes -- two scalar-cache lines, fetched by one batch of scalar loads -- where GemvArgs is
-// 480.  NWS: weights in the launch (1; 3 = fused QKV; 2 = the {gate, up} pair of the SiLU*mul epilogue).
+// one-weight launch is 120 bytes -- two scalar-cache lines, fetched by one batch of scalar loads -- where GemvArgs is
+// 440.  NWS: weights in the launch (1; 3 = fused QKV; 2 = the {gate, up} pair of the SiLU*mul epilogue).
 struct GemvM1Weight {
   const void* tiles;
   const void* scales;

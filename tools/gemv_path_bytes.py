@@ -18,8 +18,11 @@ the object and prints, per kernel:
   python tools/gemv_path_bytes.py                 # the default list of the current tree
   python tools/gemv_path_bytes.py --set headline  # the two headline instantiations only
   python tools/gemv_path_bytes.py --source OTHER/woq_gemv.hip --legacy   # a tree without the specialised kernel
+  python tools/gemv_path_bytes.py --against OTHER/woq_gemv.hip           # both sources, row by row, and per kernel
+                                                                         # whether their instruction streams are equal
 """
 import argparse
+import difflib
 import os
 import re
 import shutil
@@ -211,8 +214,9 @@ def squash(s):
     return re.sub(r"\s+", "", s).replace("(nad::ActType)", "").replace("nad::", "")
 
 
-def report(source, kernels, arch="gfx950", keep=None):
-    """[(label, template-id, figures dict)] for `kernels` [(label, (template-id, arg type))]."""
+def report(source, kernels, arch="gfx950", keep=None, with_code=False):
+    """[(label, template-id, figures dict)] for `kernels` [(label, (template-id, arg type))]; with_code appends each
+    kernel's instruction stream [(mnemonic, operands)] (no addresses, no encodings) to its row."""
     work = keep or tempfile.mkdtemp(prefix="gemv_path_")
     try:
         obj = compile_kernels(source, [k for _, k in kernels], work, arch)
@@ -244,6 +248,8 @@ def report(source, kernels, arch="gfx950", keep=None):
                                    scratch=int(meta[mi]["private_segment_fixed_size"]))
         else:
             raise RuntimeError("metadata entries (%d) do not match the kernels (%d)" % (len(meta), len(rows)))
+        if with_code:
+            return [(l, t, f, [(mn, re.sub(r"\s+", " ", ops)) for _, _, mn, ops in funcs[sym]]) for l, t, f, sym in rows]
         return [(l, t, f) for l, t, f, _ in rows]
     finally:
         if keep is None:
@@ -259,16 +265,36 @@ def main():
     ap.add_argument("--set", default="all", choices=["all", "headline"])
     ap.add_argument("--legacy", action="store_true", help="the source has no woq_gemv_m1s_kernel: list the generic ones")
     ap.add_argument("--keep", default=None, help="directory to keep the wrapper source and the object in")
+    ap.add_argument("--against", default=None, metavar="OTHER/woq_gemv.hip",
+                    help="compile the same instantiations from this source too: both rows per kernel, and whether the "
+                         "two instruction streams (mnemonics and operands) are identical")
     args = ap.parse_args()
     if hipcc_path() is None:
         sys.exit("hipcc not found")
     if args.keep:
         os.makedirs(args.keep, exist_ok=True)
-    rows = report(args.source, kernel_sets(args.legacy)[args.set], keep=args.keep)
-    print("# %s" % os.path.relpath(args.source, ROOT))
-    print("%-28s " % "kernel" + " ".join("%9s" % c for c in COLS) + "  instantiation")
-    for label, tid, f in rows:
-        print("%-28s " % label + " ".join("%9d" % f[c] for c in COLS) + "  " + tid)
+    kernels = kernel_sets(args.legacy)[args.set]
+    head = "%-28s " % "kernel" + " ".join("%9s" % c for c in COLS)
+    if args.against is None:
+        rows = report(args.source, kernels, keep=args.keep)
+        print("# %s" % os.path.relpath(args.source, ROOT))
+        print(head + "  instantiation")
+        for label, tid, f in rows:
+            print("%-28s " % label + " ".join("%9d" % f[c] for c in COLS) + "  " + tid)
+        return
+    mine = report(args.source, kernels, keep=args.keep, with_code=True)
+    other = report(args.against, kernels, with_code=True)
+    print("# a: %s\n# b: %s" % (os.path.relpath(args.source, ROOT), os.path.relpath(args.against, ROOT)))
+    print(head + "  code")
+    for (label, tid, fa, ca), (_, _, fb, cb) in zip(mine, other):
+        print("%-28s " % label + "  " + tid)
+        if ca == cb:
+            verdict = "identical"
+        else:  # how far apart: instructions of the longer stream outside the longest common subsequence blocks
+            same = sum(b.size for b in difflib.SequenceMatcher(None, ca, cb, autojunk=False).get_matching_blocks())
+            verdict = "DIFFERS (%d of %d instructions)" % (max(len(ca), len(cb)) - same, max(len(ca), len(cb)))
+        print("%-28s " % "  a" + " ".join("%9d" % fa[c] for c in COLS) + "  " + verdict)
+        print("%-28s " % "  b" + " ".join("%9d" % fb[c] for c in COLS))
 
 
 if __name__ == "__main__":
