@@ -189,6 +189,8 @@ int nad_device_forward(const void* act, int act_dtype, const void* devstor, floa
 #define NAD_KERNEL_GEMM 8      /* woq_gemm_kernel: register-staged prefill fallback */
 #define NAD_KERNEL_GEMM7 9     /* woq_gemm7_kernel: prefill, int4 groups of 128 * 2^j, scale folded (default) */
 #define NAD_KERNEL_MID 10      /* woq_mid_kernel: 12 (fp16) / 8 (fp32, bf16) <= M <= 64, int4 / int2 */
+#define NAD_KERNEL_Q6K_GEMV 11 /* woq_q6k_gemv_kernel: GGUF Q6_K, M <= 16 (sub-scales in fp32: flags bit 0 clear) */
+#define NAD_KERNEL_Q6K_GEMM 12 /* woq_q6k_gemm_kernel: GGUF Q6_K, M > 16 (sc * q folded into fp16: flags bit 0 set) */
 int nad_plan_forward(int bits, int n, int k, int blocksize, int scale_t, int asym, int m, int act_dtype, int64_t* out,
                      int nout);
 /* the same dry run for a loaded device weight (its format, act-order, fold range and compute mode included) */
@@ -245,8 +247,9 @@ int nad_get_compute_mode(void);
 /* per-thread override of the process mode (-1 clears it); thread-safe, takes precedence over nad_set_compute_mode */
 int nad_set_thread_compute_mode(int mode);
 /* per-weight arithmetic, as the reference selects it per blob core (bestla_gemm.cpp:516-616): -1 follow the
- * thread / process mode, 0 fp, 1 int8 (integer-core blobs and the GGUF types; other weights stay fp).  Takes precedence
- * over both; a fused call whose weights resolve to different arithmetic runs each weight in its own. */
+ * thread / process mode, 0 fp, 1 int8 (integer-core blobs and the legacy GGUF block types; other weights -- NFloat
+ * weights and GGUF Q6_K among them -- stay fp: the call succeeds and nad_device_get_compute keeps returning 0).  Takes
+ * precedence over both; a fused call whose weights resolve to different arithmetic runs each weight in its own. */
 int nad_device_set_compute(void* devstor, int mode);
 /* the arithmetic a forward of this weight takes now: 0 fp, 1 int8, -1 not a device weight */
 int nad_device_get_compute(const void* devstor);
@@ -289,6 +292,25 @@ size_t nad_gguf_block_bytes(int type);
 size_t nad_gguf_device_size(int type, int n, int k);
 int nad_gguf_device_load(int type, const void* blocks, int n, int k, void* devstor, void* deviceptr, size_t capacity,
                          void* queue);
+/* ===== GGUF Q6_K (the reference's NE_TYPE_Q6_K; block_q6_K, neural_speed/core/data_types.h:133-138; matmul'd at
+ * ne_layers.c:7326 through quantize_fns): a matrix of N rows x K (K % 256 == 0), rows of K/256 superblocks {u8 ql[128];
+ * u8 qh[64]; s8 scales[16]; fp16 d} (210 bytes), w = d * scales[e / 16] * q with q in -32..31.  The superblock is 256
+ * and the sub-scale group 16, so the type has entries of its own: nad_gguf_block_bytes(14) and nad_gguf_device_size(14,
+ * ...) keep returning 0 with an error naming 14.  The device layout holds the file's own 6.5625 bits per weight (6-bit
+ * quants as nibble and crumb pieces, int8 sub-scales, fp16 d: nad_q6_k_device_size(n, k) <= ceil(n / 16) * 16 *
+ * (k / 256) * 210 + 255), and the weight runs on two kernels of its own: up to 16 rows the decode GEMV, which applies the
+ * sub-scales in fp32 (results at the decode tolerance), above that a tile GEMM that folds scales * q into its fp16
+ * fragments (the folded-scale tolerance).  nad_weight_info reports bits 6, blocksize 16, scale type f16.  Every
+ * nad_device_* / bestla_device_* forward accepts the descriptor with every single-weight epilogue;
+ * nad_device_qkv_forward runs the three weights one after another when any is Q6_K; nad_device_ffn_gate_up /
+ * nad_device_ffn_forward run gate and up as two passes then, and the partner may be of any format.  Arithmetic is fp
+ * only (nad_device_set_compute(w, 1) leaves it fp: the reference's Q8_K integer dot product is not reproduced);
+ * nad_batch_create refuses a Q6_K weight.  nad_device_unpack_fp32 returns (d * sc) * q, bit for bit
+ * dequantize_row_q6_K (vectors/cpu/quantize.h:956-999). */
+#define NAD_GGUF_Q6_K 14
+/* 0 and nad_last_error() unless n > 0 and k is a positive multiple of 256 */
+size_t nad_q6_k_device_size(int n, int k);
+int nad_q6_k_device_load(const void* blocks, int n, int k, void* devstor, void* deviceptr, size_t capacity, void* queue);
 /* quantize_row_q8_1_reference (vectors/cpu/quantize.h:546-579) on device pointers: act [m][lda] -> m rows of K/32
  * blocks {float d; float s; int8 qs[32]} */
 int nad_quant_q8_1(const void* act, int act_dtype, int m, int k, int lda, void* blocks, void* queue);

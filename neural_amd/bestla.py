@@ -169,7 +169,7 @@ def split_range(blob, axis, rank, world, unit=1):
 # ---------------------------------------------------------------------------------------------------- device
 KERNELS = {1: "woq_gemv_m1_kernel", 2: "woq_gemv_kernel", 3: "woq_skinny_kernel", 4: "woq_i8_kernel",
            5: "woq_gemm3_kernel", 6: "woq_gemm4_kernel", 7: "woq_gemm2_kernel", 8: "woq_gemm_kernel",
-           9: "woq_gemm7_kernel", 10: "woq_mid_kernel"}
+           9: "woq_gemm7_kernel", 10: "woq_mid_kernel", 11: "woq_q6k_gemv_kernel", 12: "woq_q6k_gemm_kernel"}
 
 
 def plan_forward(bits, n, k, group_size=128, scale_dtype="fp16", asym=False, m=1, act="fp32"):
@@ -266,7 +266,10 @@ class DeviceWeight:
     @classmethod
     def from_gguf(cls, type, blocks, n, k, device=None, stream=None):
         """A GGUF matrix of one of the legacy block types (GGUF_Q4_0 / Q4_1 / Q5_0 / Q5_1 / Q8_0: n rows of k/32 blocks,
-        as an ne_tensor of that NE_TYPE holds it) in the device tile layout (nad_gguf_device_load)."""
+        as an ne_tensor of that NE_TYPE holds it) in the device tile layout (nad_gguf_device_load); GGUF_Q6_K goes to
+        from_q6_k."""
+        if int(type) == GGUF_Q6_K:  # superblocks of 256: entries of its own
+            return cls.from_q6_k(blocks, n, k, device=device, stream=stream)
         torch = _torch()
         L = lib()
         bb = L.nad_gguf_block_bytes(int(type))
@@ -281,6 +284,22 @@ class DeviceWeight:
         desc = (C.c_uint8 * L.bestla_device_storage_size())()
         check(L.nad_gguf_device_load(int(type), _ptr(blocks), n, k, desc, _ptr(mem), need, _stream(stream)),
               "nad_gguf_device_load")
+        return cls(_desc=desc, _mem=mem)
+
+    @classmethod
+    def from_q6_k(cls, blocks, n, k, device=None, stream=None):
+        """A GGUF Q6_K matrix (n rows of k/256 block_q6_K of 210 bytes, as an NE_TYPE_Q6_K ne_tensor holds it) in its
+        own device layout at 6.5625 bits per weight (nad_q6_k_device_load)."""
+        torch = _torch()
+        L = lib()
+        need = L.nad_q6_k_device_size(n, k)
+        if not need:
+            raise RuntimeError(last_error())
+        blocks = np.ascontiguousarray(blocks, dtype=np.uint8)
+        assert blocks.size == n * (k // 256) * 210, (blocks.size, n, k)
+        mem = torch.empty(need, dtype=torch.uint8, device=device or "cuda")
+        desc = (C.c_uint8 * L.bestla_device_storage_size())()
+        check(L.nad_q6_k_device_load(_ptr(blocks), n, k, desc, _ptr(mem), need, _stream(stream)), "nad_q6_k_device_load")
         return cls(_desc=desc, _mem=mem)
 
     def forward(self, x, out=None, epilogue=EPI_NONE, bias=None, residual=None, stream=None):
@@ -329,6 +348,7 @@ class DeviceWeight:
 COMPUTE_FP, COMPUTE_INT8 = 0, 1
 # GGUF block types (the reference's ne_type values, neural_speed/core/data_types.h)
 GGUF_Q4_0, GGUF_Q4_1, GGUF_Q5_0, GGUF_Q5_1, GGUF_Q8_0 = 2, 3, 6, 7, 8
+GGUF_Q6_K = 14  # superblocks of 256 (DeviceWeight.from_q6_k; from_gguf routes it there)
 
 
 def set_compute_mode(mode):

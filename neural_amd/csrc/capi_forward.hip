@@ -115,6 +115,8 @@ static int prepare_gemv(GemvArgs& a, int& waves, int& grid, const Act& x, const 
       return 0;
   if (w0.kmajor) return 0;  // the stream stages each stripe's scale block: stripe-major layout only
   for (int i = 0; i < W.nw; i++)
+    if (is_q6k(W[i])) return 0;  // a layout of its own (forward_q6k); run_skinny refuses it by name
+  for (int i = 0; i < W.nw; i++)
     if (W[i].f4kind >= 0) return 0;  // NFloat weights: LUT dequant lives in the skinny kernel
   int tpg = 0;
   const int gpt = gemv_groups_per_tile(w0.bits, w0.nt, w0.ng, w0.blocksize, &tpg);
@@ -181,8 +183,17 @@ static int try_gemv(const Act& x, const Weights& W, const Epi& e, hipStream_t st
 
 static int run_i8(const Act& x, const Weights& W, bool dual, const Epi& e, hipStream_t st);
 
+static bool refuse_q6k(const DeviceWeight& w, const char* path) {
+  if (!is_q6k(w)) return false;
+  set_err("a GGUF Q6_K weight reached the %s path, which cannot read its layout (Q6_K runs on woq_q6k_gemv_kernel / "
+          "woq_q6k_gemm_kernel only)", path);
+  return true;
+}
+
 static int run_skinny(const Act& x, const Weights& W, const Epi& e, hipStream_t st) {
   const int nw = W.nw;
+  for (int i = 0; i < nw; i++)
+    if (refuse_q6k(W[i], "stripe-stream / skinny decode")) return -1;
   if (nw > 1) {  // weights of one fused call whose arithmetic differs (per-weight compute modes) run one by one
     bool mixed = false;
     for (int i = 1; i < nw; i++)
@@ -377,7 +388,7 @@ struct A16 {
 // 3: gemm3 (int4, groups of 128 * 2^j); 4: gemm4 (int4 g32 / g64, int2 groups >= 64); 0: register-staged fallback
 static int pipelined_gemm(const DeviceWeight& w, int m) {
   const Knobs& kn = knobs();
-  if (kn.gemm2_disable || w.kmajor || w.f4kind >= 0 || m <= 16 ||
+  if (kn.gemm2_disable || w.kmajor || w.f4kind >= 0 || m <= 16 || is_q6k(w) ||
       uint64_t(m) * uint64_t(w.nt) * 512 >= (1ull << 32))
     return 0;
   const int tpg = w.blocksize / 128;
@@ -577,6 +588,7 @@ static int gemm7_bm(const DeviceWeight& w, int m) {
 // caller shares among weights) or the register-staged fallback
 static int run_gemm(const Act& x, const DeviceWeight& w, const Out& o, const Epi& e, hipStream_t st,
                     const A16* pre = nullptr) {
+  if (refuse_q6k(w, "mid-M / prefill GEMM")) return -1;
   if (int8_compute(w)) return run_i8(x, One(w, o), false, e, st);
   {
     const int r = run_mid(x, w, o, e, st);
@@ -702,7 +714,40 @@ static int forward_min(const Act& x, const DeviceWeight& w, const Out& o, const 
   if (forward_one(x, w, o, Epi{}, st)) return -1;
   return min_term(x, Sums{}, w, o, e, st);
 }
+// A GGUF Q6_K weight (woq_q6k.hip): the decode GEMV up to 16 rows -- sub-scales applied in fp32, plan fold 0 -- and the
+// register-staged GEMM above, which folds sc * q into its fp16 fragments (plan fold 1).  Both apply the epilogue
+// themselves (gemm_epilogue4: every single-weight kind and the multiply by aux of the FFN's second pass).
+static int forward_q6k(const Act& x, const DeviceWeight& w, const Out& o, const Epi& e, hipStream_t st) {
+  if (o.h16 || e.kind == kEpiGeluMul) {
+    set_err("Q6_K: fp16 GEMM output and the fused dual epilogues are not available (the FFN entries run two passes)");
+    return -1;
+  }
+  GemmArgs a{};
+  fill_act(a, x);
+  fill_epi(a, e);
+  a.scale_t = w.scale_t;
+  a.vec_ok = vec_aligned(x) ? 1 : 0;
+  a.w = view(w, o.p, o.ld, e);
+  if (x.m <= kSkinnyMaxM) {
+    Q6kGemvGeom g{};
+    if (!q6k_gemv_geometry(x.m, x.k, w.ns, x.t, device_cus(), &g)) {
+      set_err("Q6_K decode: K = %d is too long for the kernel's LDS staging of one activation row", x.k);
+      return -1;
+    }
+    return launch(planned(NAD_KERNEL_Q6K_GEMV, g.grid * g.passes, g.waves * 64, 1, 0), "Q6_K gemv kernel",
+                  [&] { return launch_q6k_gemv(a, x.t, g, st); })
+               ? 0
+               : -1;
+  }
+  a.fold = 1;
+  const int tiles = ((x.m + 127) / 128) * ((w.ns + 7) / 8);
+  return launch(planned(NAD_KERNEL_Q6K_GEMM, tiles, 512, 1, 1), "Q6_K gemm kernel",
+                [&] { return launch_q6k_gemm(a, x.t, st); })
+             ? 0
+             : -1;
+}
 static int forward_any(const Act& x, const DeviceWeight& w, const Out& o, const Epi& e, hipStream_t st) {
+  if (is_q6k(w)) return forward_q6k(x, w, o, e, st);
   return w.mins ? forward_min(x, w, o, e, st) : forward_one(x, w, o, e, st);
 }
 
@@ -873,7 +918,8 @@ extern "C" int nad_device_qkv_forward(const void* act, int act_dtype, const void
   int ldos[3] = {ldo_q, ldo_k, ldo_v};
   const Weights W{3, ws, outs, ldos};
   const Act x{act, act_dtype, lda, m, k};
-  if (ws[0]->mins || ws[1]->mins || ws[2]->mins) {  // block mins: the three weights one after another
+  // block mins or a Q6_K weight: the three weights one after another
+  if (ws[0]->mins || ws[1]->mins || ws[2]->mins || is_q6k(*ws[0]) || is_q6k(*ws[1]) || is_q6k(*ws[2])) {
     for (int i = 0; i < 3; i++)
       if (forward_any(x, W[i], Out{outs[i], ldos[i]}, Epi{}, st)) return -1;
     return 0;
@@ -930,19 +976,21 @@ extern "C" int nad_device_ffn_gate_up(const void* act, int act_dtype, const void
     set_err("ffn epilogue must be SILU_MUL or GELU_MUL");
     return -1;
   }
-  if (w1->n != fmid || w3->n != fmid || w1->k != fin || w3->k != fin || !same_kind(*w1, *w3)) {
+  // a pair with a Q6_K weight runs as two single-weight passes: the two need not share a format
+  const bool q6k = is_q6k(*w1) || is_q6k(*w3);
+  if (w1->n != fmid || w3->n != fmid || w1->k != fin || w3->k != fin || (!q6k && !same_kind(*w1, *w3))) {
     set_err("FFN gate/up shapes do not match (fin=%d fmid=%d)", fin, fmid);
     return -1;
   }
   hipStream_t st = static_cast<hipStream_t>(queue);
   const Act x{act, act_dtype, lda, m, fin};
   const Out up{tmp2, fmid};
-  if (w1->mins || w3->mins) {
+  if (w1->mins || w3->mins || q6k) {
     // block mins: two passes as run_i8's -- t1 = act(x.w1), tmp2 = t1 * (x.w3) -- each a main launch and the min-term
     // pass, which applies the activation / the multiply.  Without tmp1, t1 lies in the workspace behind the part the
     // passes' own kernels use (nad_device_workspace_size).
-    if (int8_compute(*w1) != int8_compute(*w3) ||
-        (int8_compute(*w1) && gguf_act_quant(*w1) != gguf_act_quant(*w3))) {
+    if (!q6k && (int8_compute(*w1) != int8_compute(*w3) ||
+                 (int8_compute(*w1) && gguf_act_quant(*w1) != gguf_act_quant(*w3)))) {
       set_err("gate/up weights of one FFN must resolve to the same arithmetic (nad_device_set_compute) and, in the "
               "int8 mode, to one activation quantizer");
       return -1;
@@ -958,6 +1006,7 @@ extern "C" int nad_device_ffn_gate_up(const void* act, int act_dtype, const void
     // activation always, the multiply by t1 in the prefill GEMMs and the int8 kernel (the M <= 16 fp kernels take the
     // multiply only as a fused pair, so there the min-term kernel runs as the epilogue alone)
     if (forward_any(x, *w1, Out{t1, fmid}, Epi::gate_of(epi), st)) return -1;
+    if (is_q6k(*w3)) return forward_q6k(x, *w3, up, Epi::mul(t1, fmid), st);
     if (!w3->mins && m > kSkinnyMaxM) return run_gemm(x, *w3, up, Epi::mul(t1, fmid), st);
     return forward_min(x, *w3, up, Epi::mul(t1, fmid), st);
   }
@@ -995,14 +1044,15 @@ int ffn_forward(const void* act, int act_dtype, const void* w1p, const void* w2p
     return -1;
   }
   if (w1->n != fmid || w3->n != fmid || w1->k != fin || w3->k != fin || w2->k != fmid || w2->n != fout ||
-      !same_kind(*w1, *w3)) {
+      (!is_q6k(*w1) && !is_q6k(*w3) && !same_kind(*w1, *w3))) {
     set_err("FFN shapes do not match (fin=%d fmid=%d fout=%d)", fin, fmid, fout);
     return -1;
   }
   hipStream_t st = static_cast<hipStream_t>(queue);
   const Out down{out, fout};
   const bool any_mins = w1->mins || w2->mins || w3->mins;
-  if (!any_mins && f16_tmp && m > kSkinnyMaxM && tmp1 && ffn16_ok(*w1, *w2, *w3, m, fmid)) {
+  const bool any_q6k = is_q6k(*w1) || is_q6k(*w2) || is_q6k(*w3);
+  if (!any_mins && !any_q6k && f16_tmp && m > kSkinnyMaxM && tmp1 && ffn16_ok(*w1, *w2, *w3, m, fmid)) {
     // prefill with fp16 intermediates: gate -> act(x.w1) as fp16 in tmp1, up -> act(x.w1) * (x.w3) as fp16 in tmp2,
     // which IS down's fp16 A operand (fmid = whole K tiles): no fp32 round trip, no conversion pass before down
     const Act x{act, act_dtype, lda, m, fin};
@@ -1022,6 +1072,7 @@ int ffn_forward(const void* act, int act_dtype, const void* w1p, const void* w2p
   }
   if (nad_device_ffn_gate_up(act, act_dtype, w1p, w3p, tmp1, tmp2, m, fin, fmid, lda, epi, queue)) return -1;
   const Act t{tmp2, kActF32, fmid, m, fmid};
+  if (is_q6k(*w2)) return forward_q6k(t, *w2, down, Epi{}, st);
   if (w2->mins) return forward_min(t, *w2, down, Epi{}, st);
   if (m <= kSkinnyMaxM) return run_skinny(t, One(*w2, down), Epi{}, st);
   return run_gemm(t, *w2, down, Epi{}, st);
@@ -1051,6 +1102,10 @@ extern "C" void* nad_batch_create(const nad_batch_problem* p, int n) {
   for (int i = 0; i < n; i++) {
     const DeviceWeight* w = as_weight(p[i].weight);
     if (!w) return nullptr;
+    if (is_q6k(*w)) {  // the batched GEMV streams the int4 / int2 tile layouts only
+      set_err("nad_batch_create: problem %d's weight is GGUF Q6_K, which is not batched", i);
+      return nullptr;
+    }
     if (w->n != w0->n || w->k != w0->k || w->bits != w0->bits || w->blocksize != w0->blocksize ||
         w->asym != w0->asym || w->scale_t != w0->scale_t || w->nt != w0->nt || w->ng != w0->ng ||
         w->kmajor != w0->kmajor || w->f4kind != w0->f4kind) {

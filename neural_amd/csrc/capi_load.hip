@@ -305,8 +305,12 @@ extern "C" size_t nad_gguf_block_bytes(int type) {
     case NAD_GGUF_Q5_0: return 22;
     case NAD_GGUF_Q5_1: return 24;
     case NAD_GGUF_Q8_0: return 34;
+    case NAD_GGUF_Q6_K:  // superblocks of 256, not blocks of 32: entries of its own
+      set_err("GGUF type 14 (Q6_K) has no 32-element block: it loads through nad_q6_k_device_size / nad_q6_k_device_load");
+      return 0;
     default:
-      set_err("GGUF type %d is not supported (Q4_0 = 2, Q4_1 = 3, Q5_0 = 6, Q5_1 = 7, Q8_0 = 8)", type);
+      set_err("GGUF type %d is not supported (Q4_0 = 2, Q4_1 = 3, Q5_0 = 6, Q5_1 = 7, Q8_0 = 8; Q6_K = 14 through "
+              "nad_q6_k_device_load)", type);
       return 0;
   }
 }
@@ -397,6 +401,60 @@ extern "C" int nad_gguf_device_load(int type, const void* blocks, int n, int k, 
   }
   if (e != hipSuccess) {
     set_err("nad_gguf_device_load: %s failed: %s", what, hipGetErrorString(e));
+    return -1;
+  }
+  std::memcpy(devstor, &w, sizeof(w));
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ GGUF Q6_K
+extern "C" size_t nad_q6_k_device_size(int n, int k) {
+  if (n <= 0 || k <= 0 || k % 256) {
+    set_err("Q6_K needs n > 0 and k a positive multiple of 256 (n=%d k=%d)", n, k);
+    return 0;
+  }
+  DeviceWeight w{};
+  return q6k_geometry(w, n, k);
+}
+
+extern "C" int nad_q6_k_device_load(const void* blocks, int n, int k, void* devstor, void* deviceptr, size_t capacity,
+                                    void* queue) {
+  const size_t need = nad_q6_k_device_size(n, k);
+  if (!need) return -1;
+  if (!blocks || !devstor || !deviceptr || capacity < need) {
+    set_err("nad_q6_k_device_load: null pointer or device buffer too small (need %zu, have %zu)", need, capacity);
+    return -1;
+  }
+  hipStream_t st = static_cast<hipStream_t>(queue);
+  DeviceWeight w{};
+  q6k_geometry(w, n, k);
+  q6k_assign(w, deviceptr);
+  w.src_core_id = kGgufQ6_K;
+  w.owner = nullptr;
+  w.fold_ok = 0;  // sc * q is folded by the Q6_K GEMM itself (|sc * q| <= 4096 always fits fp16), d never
+  const size_t bytes = size_t(n) * (k / 256) * 210;
+  uint8_t* stage = nullptr;
+  HIP_OK(hipMalloc(&stage, bytes));
+  // copy, repack (it writes every byte of the layout, the padding columns included), wait; the staging buffer is
+  // freed on every way out
+  const char* what = "hipMemcpyAsync of the blocks";
+  hipError_t e = hipMemcpyAsync(stage, blocks, bytes, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) {
+    what = "Q6_K repack launch";
+    e = launch_q6k_repack(stage, n, k, w, st);
+  }
+  const hipError_t es = hipStreamSynchronize(st);
+  if (e == hipSuccess && es != hipSuccess) {
+    what = "hipStreamSynchronize";
+    e = es;
+  }
+  const hipError_t ef = hipFree(stage);
+  if (e == hipSuccess && ef != hipSuccess) {
+    what = "hipFree of the staging buffer";
+    e = ef;
+  }
+  if (e != hipSuccess) {
+    set_err("nad_q6_k_device_load: %s failed: %s", what, hipGetErrorString(e));
     return -1;
   }
   std::memcpy(devstor, &w, sizeof(w));
@@ -563,8 +621,12 @@ extern "C" int nad_device_unpack_fp32(const void* devstor, float* host_out, void
   float* d = nullptr;
   size_t bytes = size_t(w->n) * w->k * 4;
   HIP_OK(hipMalloc(&d, bytes));
-  hipLaunchKernelGGL(nad_unrepack_kernel, dim3(2048), dim3(256), 0, st, *w, d);
-  HIP_OK(hipGetLastError());
+  if (is_q6k(*w)) {
+    HIP_OK(launch_q6k_unpack(*w, d, st));
+  } else {
+    hipLaunchKernelGGL(nad_unrepack_kernel, dim3(2048), dim3(256), 0, st, *w, d);
+    HIP_OK(hipGetLastError());
+  }
   HIP_OK(hipMemcpyAsync(host_out, d, bytes, hipMemcpyDeviceToHost, st));
   HIP_OK(hipStreamSynchronize(st));
   HIP_OK(hipFree(d));

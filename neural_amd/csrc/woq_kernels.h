@@ -257,6 +257,21 @@ hipError_t launch_block_sums(const void* A, int act_t, int lda, int M, int K, fl
 hipError_t launch_min_term(const MinTermArgs& a, int act_t, hipStream_t stream);        // M <= kMinTermSmallM
 hipError_t launch_min_term_tiled(const MinTermArgs& a, hipStream_t stream);            // any M, S given
 hipError_t launch_q8_0_quant(const Q80Args& a, int act_t, hipStream_t stream);
+// GGUF Q6_K (woq_q6k.hip; the layout: woq_layout.h).  src: n rows of k/256 block_q6_K on the device
+hipError_t launch_q6k_repack(const uint8_t* src, int n, int k, const DeviceWeight& w, hipStream_t stream);
+// (d * sc) * q in fp32, [K][N]
+hipError_t launch_q6k_unpack(const DeviceWeight& w, float* out, hipStream_t stream);
+// Geometry of a woq_q6k_gemv_kernel launch of m <= 16 rows: activation rows per pass (a pass streams the whole weight
+// for the rows whose fp16 staging fits LDS beside the partial-sum slots), passes and LDS bytes; false when not even one
+// row fits (K > 65536 / 2 for fp32 / bf16 rows)
+struct Q6kGemvGeom {
+  int rows_pp, passes, grid, waves;
+  size_t lds;
+};
+bool q6k_gemv_geometry(int m, int k, int ns, int act_t, int cus, Q6kGemvGeom* g);
+// a: A / lda / M / K, the epilogue operands and a.w (tiles = quants, zps = sub-scales, scales = d, nt = superblocks)
+hipError_t launch_q6k_gemv(const GemmArgs& a, int act_t, const Q6kGemvGeom& g, hipStream_t stream);
+hipError_t launch_q6k_gemm(const GemmArgs& a, int act_t, hipStream_t stream);  // grid: ceil(M / 128) * ceil(ns / 8)
 hipError_t launch_quant_u8(const QuantU8Args& a, int act_t, hipStream_t stream);
 hipError_t launch_i8(const I8Args& a, int bits, hipStream_t stream);
 hipError_t launch_gemm4(const GemmArgs& a, int bits, const _Float16* A16, int lda16, hipStream_t stream);

@@ -22,6 +22,22 @@
 //            reads it: woq_min_term_kernel (woq_gguf.hip) adds X's block sums times the mins after the main kernel.
 //            Q4_1's q in 0..15 does not fit the symmetric nibble (q + 8): the nibble holds q, the kernels decode q - 8,
 //            and the min-term pass adds the block sums times 8 d as well (DeviceWeight::min_bias)
+//
+// GGUF Q6_K (bits = 6, blocksize = 16; w = d * sc * q, q in -32..31, an int8 sc per 16 weights, an fp16 d per 256) has
+// a layout of its own at the file's 6.5625 bits per weight, built for v_mfma_f32_16x16x16_f16, whose 16-deep K is one
+// sub-scale group: lane l supplies B[k = 4 (l >> 4) + j][n = l & 15], j = 0..3.  Per (stripe s, superblock b) of 256 k:
+//   tiles  : [ns][k/256][3 pieces][64 lanes][16 B] -- 3 KiB, the stored value v = q + 32 split into nibble and crumb:
+//            pieces 0, 1: the low nibbles of groups 0..7 / 8..15.  Dword dd of lane l holds groups 2 dd, 2 dd + 1 of
+//              its piece; nibble position p: group 2 dd + ((p & 3) >> 1), element j = 2 (p & 1) + (p >> 2)
+//            piece 2: the high crumbs of all 16 groups.  Dword w holds groups 4 w .. 4 w + 3; crumb position p: group
+//              4 w + ((p & 7) >> 1), j = 2 (p & 1) + (p >> 3)
+//            so for the i-th pair of a group ((lo >> 4 i) & 0x000F000F) | (((hi >> 2 i') & 0x00030003) << 4) | 0x64006400
+//            is the fp16 pair (1024 + v_j, 1024 + v_j+1), and minus 1056 the pair of q.  Element j of group g of lane
+//            l is k = 256 b + 16 g + 4 (l >> 4) + j.
+//   zps    : the sub-scales, int8 [ns][k/256][16 n][16 groups]: lane l reads the 16 of its column with one 16-B load
+//   scales : d, fp16 [ns][k/256][16 n]
+// Padding columns of the last stripe hold v = 32 (q = 0), sc = 0 and d = 0.  asym stays 0: zps is no zero point here,
+// and no kernel but woq_q6k.hip's reads a bits = 6 weight.
 #pragma once
 #include <cstdint>
 
@@ -127,6 +143,36 @@ inline void layout_assign(DeviceWeight& w, void* base) {
   p += w.has_shuffle ? align256(uint64_t(w.k) * 4) : 0;
   w.reduce = w.red_ld ? p : nullptr;
   p += align256(uint64_t(w.ng) * w.red_ld * 2);
+  w.bytes = uint64_t(p - static_cast<char*>(base));
+}
+
+// GGUF Q6_K (see the head of this file): geometry and the device bytes -- ns * (k / 256) * (3072 + 256 + 32), i.e. 210
+// bytes per 256 weights as in the file, plus at most 255 bytes of alignment after the d region
+inline uint64_t q6k_geometry(DeviceWeight& w, int n, int k) {
+  w = DeviceWeight{};
+  w.magic = kWeightMagic;
+  w.bits = 6;
+  w.n = n;
+  w.k = k;
+  w.blocksize = 16;
+  w.ns = (n + 15) / 16;
+  w.nt = k / 256;
+  w.ng = k / 16;
+  w.scale_t = kScaleF16;
+  w.blob_bs = 16;
+  w.f4kind = -1;
+  const uint64_t sb = uint64_t(w.ns) * w.nt;
+  return align256(sb * 3072) + align256(sb * 256) + align256(sb * 32);
+}
+inline void q6k_assign(DeviceWeight& w, void* base) {
+  char* p = static_cast<char*>(base);
+  const uint64_t sb = uint64_t(w.ns) * w.nt;
+  w.tiles = p;
+  p += align256(sb * 3072);
+  w.zps = reinterpret_cast<int8_t*>(p);
+  p += align256(sb * 256);
+  w.scales = p;
+  p += align256(sb * 32);
   w.bytes = uint64_t(p - static_cast<char*>(base));
 }
 

@@ -1,0 +1,490 @@
+// woq_q6k.hip -- GGUF Q6_K weights (neural_speed/core/data_types.h:133-138; dequantize_row_q6_K,
+// vectors/cpu/quantize.h:956-999) at the file's own 6.5625 bits per weight: the repack into the layout of woq_layout.h,
+// the unpack check, and the two forward kernels.
+//
+// A superblock is 256 weights w = d * sc * q: q in -32..31 (low nibbles in ql, high crumbs in qh), an int8 sc per 16
+// weights, one fp16 d.  The quantizer writes sc up to +-127, so |sc * q| reaches 4096 and an fp16 B fragment holding
+// sc * q is rounded (fp16 is exact only to 2048): at decode that costs 1.4e-4 .. 2.4e-4 of max|y|, seven to twelve
+// times the 2e-5 bar.  So woq_q6k_gemv_kernel keeps q alone in the fp16 fragment (exact), multiplies one group of 16
+// per v_mfma_f32_16x16x16_f16 -- whose K is exactly one group -- into a fresh accumulator, and applies float(sc) and
+// then d in fp32.  woq_q6k_gemm_kernel (M > 16) folds sc * q into the fragment, rounded once (<= 2^-11 relative, the
+// project's FOLD_TOL class), runs v_mfma_f32_16x16x32_f16 over two groups at a time and applies d per superblock.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <type_traits>
+
+#include "woq_device.h"
+#include "woq_kernels.h"
+#include "woq_layout.h"
+
+namespace nad {
+
+typedef _Float16 h4_t __attribute__((ext_vector_type(4)));
+
+constexpr int kQ6kBlockBytes = 210;  // ql[128] qh[64] scales[16] d
+constexpr int kQ6kWaves = 16;        // waves of a GEMV workgroup = K-slices of a stripe
+constexpr size_t kQ6kLdsMax = 160 * 1024;
+constexpr size_t kQ6kPartBytes = 2 * kQ6kWaves * 1024;  // two sets of per-wave 16 x 16 fp32 partials
+
+// ------------------------------------------------------------------------------------------------ repack / unpack
+// the stored 6-bit value v = q + 32 of element e of a block_q6_K: h = e / 128, j = (e % 128) / 32, l = e % 32; nibble
+// ql[64 h + 32 (j & 1) + l] (low half for j < 2), crumb (qh[32 h + l] >> 2 j) & 3
+__device__ __forceinline__ uint32_t q6k_value(const uint8_t* blk, int e) {
+  const int h = e >> 7, j = (e & 127) >> 5, l = e & 31;
+  const uint32_t ql = blk[64 * h + 32 * (j & 1) + l];
+  const uint32_t nib = j < 2 ? (ql & 15u) : (ql >> 4);
+  const uint32_t crumb = (uint32_t(blk[128 + 32 * h + l]) >> (2 * j)) & 3u;
+  return nib | (crumb << 4);
+}
+
+// one thread per (row of the padded ns * 16, superblock): 210 bytes in; 48 dwords of the three pieces, 16 sub-scales
+// and d out.  Rows past n write v = 32, sc = 0, d = 0, so nothing of the layout is left unwritten.
+__global__ void nad_q6k_repack_kernel(const uint8_t* __restrict__ src, int n, int k, DeviceWeight w) {
+  const int nsb = k / 256;
+  const int64_t idx = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (idx >= int64_t(w.ns) * 16 * nsb) return;
+  const int row = int(idx / nsb), b = int(idx % nsb);
+  const bool real = row < n;
+  const uint8_t* blk = src + (size_t(real ? row : 0) * nsb + b) * kQ6kBlockBytes;
+  const int s = row >> 4, nl = row & 15;
+  const size_t sb = size_t(s) * nsb + b;
+  uint32_t* tiles = static_cast<uint32_t*>(w.tiles) + sb * 768;
+  for (int kq = 0; kq < 4; kq++) {
+    uint32_t* lane = tiles + (kq * 16 + nl) * 4;
+    for (int pc = 0; pc < 2; pc++)
+      for (int dd = 0; dd < 4; dd++) {
+        uint32_t word = 0;
+        for (int p = 0; p < 8; p++) {
+          const int g = 8 * pc + 2 * dd + ((p & 3) >> 1), j = 2 * (p & 1) + (p >> 2);
+          const uint32_t v = real ? q6k_value(blk, 16 * g + 4 * kq + j) : 32u;
+          word |= (v & 15u) << (4 * p);
+        }
+        lane[pc * 256 + dd] = word;
+      }
+    for (int wd = 0; wd < 4; wd++) {
+      uint32_t word = 0;
+      for (int p = 0; p < 16; p++) {
+        const int g = 4 * wd + ((p & 7) >> 1), j = 2 * (p & 1) + (p >> 3);
+        const uint32_t v = real ? q6k_value(blk, 16 * g + 4 * kq + j) : 32u;
+        word |= (v >> 4) << (2 * p);
+      }
+      lane[512 + wd] = word;
+    }
+  }
+  int8_t* sc = w.zps + (sb * 16 + nl) * 16;
+  for (int g = 0; g < 16; g++) sc[g] = real ? int8_t(blk[192 + g]) : int8_t(0);
+  static_cast<uint16_t*>(w.scales)[sb * 16 + nl] = real ? uint16_t(blk[208] | (uint16_t(blk[209]) << 8)) : uint16_t(0);
+}
+
+// the layout back to fp32 [K][N]: (d * sc) * q with dequantize_row_q6_K's association, no contraction
+__global__ void nad_q6k_unpack_kernel(DeviceWeight w, float* out) {
+#pragma clang fp contract(off)
+  const int nsb = w.nt;
+  const uint64_t total = uint64_t(w.n) * w.k;
+  for (uint64_t i = blockIdx.x * uint64_t(blockDim.x) + threadIdx.x; i < total; i += uint64_t(gridDim.x) * blockDim.x) {
+    const int kk = int(i / w.n), n = int(i % w.n);
+    const int s = n >> 4, nl = n & 15, b = kk >> 8, g = (kk & 255) >> 4, kq = (kk & 15) >> 2, j = kk & 3;
+    const size_t sb = size_t(s) * nsb + b;
+    const uint32_t* lane = static_cast<const uint32_t*>(w.tiles) + sb * 768 + (kq * 16 + nl) * 4;
+    const int pl = 2 * (g & 1) + (j >> 1) + 4 * (j & 1);          // nibble position in dword (g & 7) >> 1 of piece g >> 3
+    const int ph = 2 * (g & 3) + (j >> 1) + 8 * (j & 1);          // crumb position in dword g >> 2 of piece 2
+    const uint32_t nib = (lane[(g >> 3) * 256 + ((g & 7) >> 1)] >> (4 * pl)) & 15u;
+    const uint32_t crumb = (lane[512 + (g >> 2)] >> (2 * ph)) & 3u;
+    const int q = int(nib | (crumb << 4)) - 32;
+    const float d = float(static_cast<const _Float16*>(w.scales)[sb * 16 + nl]);
+    const float ds = d * float(int(w.zps[(sb * 16 + nl) * 16 + g]));
+    out[i] = ds * float(q);
+  }
+}
+
+hipError_t launch_q6k_repack(const uint8_t* src, int n, int k, const DeviceWeight& w, hipStream_t st) {
+  const int64_t total = int64_t(w.ns) * 16 * (k / 256);
+  hipLaunchKernelGGL(nad_q6k_repack_kernel, dim3(int((total + 127) / 128)), dim3(128), 0, st, src, n, k, w);
+  return hipGetLastError();
+}
+
+hipError_t launch_q6k_unpack(const DeviceWeight& w, float* out, hipStream_t st) {
+  hipLaunchKernelGGL(nad_q6k_unpack_kernel, dim3(2048), dim3(256), 0, st, w, out);
+  return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------ shared pieces
+// The fp16 pair (q_j, q_j+1) of pair i of a group: lo already shifted right by 4 i, hi shifted so that its crumb pair
+// sits at bits 4..5 / 20..21 (q6k_hi_at4)
+__device__ __forceinline__ h2_t q6k_pair(uint32_t lo_sh, uint32_t hi_at4, h2_t m1056) {
+  const uint32_t t = dq_and_or(lo_sh, 0x000F000Fu, 0x64006400u);
+  return as_h2(dq_and_or(hi_at4, 0x00300030u, t)) + m1056;
+}
+// the crumb pair at position i (bits 2 i, 2 i + 16) of hi moved to bits 4 / 20
+template <int I>
+__device__ __forceinline__ uint32_t q6k_hi_at4(uint32_t hi) {
+  if constexpr (2 * I >= 4) return hi >> (2 * I - 4);
+  return hi << (4 - 2 * I);
+}
+// the four q of group G (0..15) of a superblock this lane holds, as an MFMA 16x16x16 B fragment
+template <int G>
+__device__ __forceinline__ h4_t q6k_group(const u4_t& lo0, const u4_t& lo1, const u4_t& hi, h2_t m1056) {
+  const uint32_t lo = (G < 8 ? lo0 : lo1)[(G & 7) >> 1];
+  const uint32_t hw = hi[G >> 2];
+  constexpr int IL = 2 * (G & 1), IH = 2 * (G & 3);
+  const h2_t p0 = q6k_pair(lo >> (4 * IL), q6k_hi_at4<IH>(hw), m1056);
+  const h2_t p1 = q6k_pair(lo >> (4 * IL + 4), q6k_hi_at4<IH + 1>(hw), m1056);
+  return h4_t{p0[0], p0[1], p1[0], p1[1]};
+}
+__device__ __forceinline__ int q6k_sc(const u4_t& sc, int g) {  // sub-scale g of the lane's 16
+  return __builtin_amdgcn_sbfe(int(sc[g >> 2]), 8 * (g & 3), 8);
+}
+// d of column nl from the 16 bytes holding columns 8 (nl >> 3) .. + 7
+__device__ __forceinline__ float q6k_d(const u4_t& dv, int nl) {
+  const uint32_t lo2 = (nl & 2) ? dv[1] : dv[0], hi2 = (nl & 2) ? dv[3] : dv[2];
+  const uint32_t wsel = (nl & 4) ? hi2 : lo2;
+  return f16_bits_to_f32(uint16_t((nl & 1) ? (wsel >> 16) : (wsel & 0xffffu)));
+}
+
+// ------------------------------------------------------------------------------------------------ GEMV, M <= 16
+// Workgroups own whole stripes (blockIdx.x, + gridDim.x, ...); the 16 waves of a workgroup own the superblocks
+// b = wave, wave + 16, ... of each (any superblock count; a wave without one adds zeros).  blockIdx.y selects a pass of
+// rows_pp activation rows (q6k_gemv_geometry).  A wave sends the three 16-B-per-lane nontemporal loads of its first
+// superblock, its sub-scales and d before anything else, then the workgroup stages the pass's activations into LDS as
+// fp16 rows -- the rows themselves for fp16 activations, a hi and a lo row per activation row (x = hi + lo to 2^-22)
+// for fp32 / bf16 -- with the 16-byte chunks of row r XORed by r (the fragment reads are then conflict-free).  While a
+// superblock is multiplied the next one (of the next stripe at the end) is in flight.  Per group: q (exact fp16)
+// through one 16x16x16 MFMA onto C = 0, then acc_sb += float(sc) * p; per superblock acc += d * acc_sb.  The waves'
+// 16 x 16 partials meet in LDS (two sets, by stripe parity: one barrier per stripe) and one wave, taking turns, sums
+// them in wave order, adds lo to hi rows and runs gemm_epilogue4.  No atomics, no workspace: the same inputs give the
+// same bits on every launch.
+struct Q6kGemvArgs {
+  GemmArgs g;
+  int rows_pp;
+};
+
+template <int AT>
+__global__ __launch_bounds__(kQ6kWaves * 64) void woq_q6k_gemv_kernel(Q6kGemvArgs qa) {
+  extern __shared__ __attribute__((aligned(16))) char q6k_lds[];
+  constexpr bool HILO = AT != kActF16;
+  const GemmArgs& a = qa.g;
+  const SkinnyWeight& W = a.w;
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave-uniform: scalar
+  const int nl = lane & 15, kq = lane >> 4;
+  const int nsb = W.nt, ns = W.ns, K = a.K;
+  const int row0 = blockIdx.y * qa.rows_pp;
+  const int mloc = min(qa.rows_pp, a.M - row0);
+  const int rows = HILO ? 2 * mloc : mloc;                         // fp16 rows in LDS
+  const size_t row_bytes = size_t(K) * 2;
+  float* part = reinterpret_cast<float*>(q6k_lds + size_t(HILO ? 2 * qa.rows_pp : qa.rows_pp) * row_bytes);
+
+  const u4_t* qp = static_cast<const u4_t*>(W.tiles);
+  const u4_t* scp = reinterpret_cast<const u4_t*>(W.zps);
+  const u4_t* dp = static_cast<const u4_t*>(W.scales);
+  const bool has = wave < nsb;
+  u4_t c0{}, c1{}, c2{}, csc{}, cd{};
+  auto fetch = [&](int s, int b, u4_t& l0, u4_t& l1, u4_t& h, u4_t& sc, u4_t& d) {
+    const size_t sb = size_t(s) * nsb + b;
+    const u4_t* t = qp + sb * 192 + lane;
+    l0 = __builtin_nontemporal_load(t);
+    l1 = __builtin_nontemporal_load(t + 64);
+    h = __builtin_nontemporal_load(t + 128);
+    sc = __builtin_nontemporal_load(scp + sb * 16 + nl);
+    d = __builtin_nontemporal_load(dp + sb * 2 + (nl >> 3));
+  };
+  int s = blockIdx.x;
+  if (has && s < ns) fetch(s, wave, c0, c1, c2, csc, cd);
+
+  // stage the activations: one 8-element chunk per thread and step
+  {
+    const int chunks = K / 8;
+    const bool vec_ok = a.vec_ok != 0;
+    for (int i = threadIdx.x; i < mloc * chunks; i += kQ6kWaves * 64) {
+      const int r = i / chunks, c = i % chunks;
+      float v[8];
+      load_a8<AT>(a.A, a.lda, row0 + r, c * 8, K, nullptr, vec_ok, v);
+      h8_t hi;
+#pragma unroll
+      for (int j = 0; j < 8; j++) hi[j] = _Float16(v[j]);
+      if constexpr (HILO) {
+        h8_t lo;
+#pragma unroll
+        for (int j = 0; j < 8; j++) lo[j] = _Float16(v[j] - float(hi[j]));
+        *reinterpret_cast<h8_t*>(q6k_lds + size_t(2 * r) * row_bytes + size_t(c ^ ((2 * r) & 15)) * 16) = hi;
+        *reinterpret_cast<h8_t*>(q6k_lds + size_t(2 * r + 1) * row_bytes + size_t(c ^ ((2 * r + 1) & 15)) * 16) = lo;
+      } else {
+        *reinterpret_cast<h8_t*>(q6k_lds + size_t(r) * row_bytes + size_t(c ^ (r & 15)) * 16) = hi;
+      }
+    }
+  }
+  __syncthreads();
+
+  const h2_t m1056 = h2_splat(-1056.f);
+  const f4_t zero4{0.f, 0.f, 0.f, 0.f};
+  // this lane's A fragments: row nl of LDS, four fp16 at k = 256 b + 16 g + 4 kq.  A lane past the staged rows reads
+  // row 0 instead (in bounds, finite): its row of the product is one nobody reads
+  const bool arow = nl < rows;
+  const char* abase = q6k_lds + size_t(arow ? nl : 0) * row_bytes + (kq & 1) * 8;
+  for (int it = 0; s < ns; s += gridDim.x, it++) {
+    f4_t acc = zero4;
+    if (has) {
+      for (int b = wave; b < nsb; b += kQ6kWaves) {
+        int s2 = s, b2 = b + kQ6kWaves;
+        if (b2 >= nsb) {
+          s2 = s + gridDim.x;
+          b2 = wave;
+        }
+        u4_t n0 = c0, n1 = c1, n2 = c2, nsc = csc, nd = cd;
+        if (s2 < ns) fetch(s2, b2, n0, n1, n2, nsc, nd);
+        f4_t sbacc = zero4;
+        auto group = [&](auto gc) {
+          constexpr int G = decltype(gc)::value;
+          const h4_t af = *reinterpret_cast<const h4_t*>(abase + size_t((32 * b + 2 * G + (kq >> 1)) ^ nl) * 16);
+          const f4_t p = __builtin_amdgcn_mfma_f32_16x16x16f16(af, q6k_group<G>(c0, c1, c2, m1056), zero4, 0, 0, 0);
+          const float scf = float(q6k_sc(csc, G));
+#pragma unroll
+          for (int r = 0; r < 4; r++) sbacc[r] = __builtin_fmaf(scf, p[r], sbacc[r]);
+        };
+        group(std::integral_constant<int, 0>{});
+        group(std::integral_constant<int, 1>{});
+        group(std::integral_constant<int, 2>{});
+        group(std::integral_constant<int, 3>{});
+        group(std::integral_constant<int, 4>{});
+        group(std::integral_constant<int, 5>{});
+        group(std::integral_constant<int, 6>{});
+        group(std::integral_constant<int, 7>{});
+        group(std::integral_constant<int, 8>{});
+        group(std::integral_constant<int, 9>{});
+        group(std::integral_constant<int, 10>{});
+        group(std::integral_constant<int, 11>{});
+        group(std::integral_constant<int, 12>{});
+        group(std::integral_constant<int, 13>{});
+        group(std::integral_constant<int, 14>{});
+        group(std::integral_constant<int, 15>{});
+        const float df = q6k_d(cd, nl);
+#pragma unroll
+        for (int r = 0; r < 4; r++) acc[r] = __builtin_fmaf(df, sbacc[r], acc[r]);
+        c0 = n0;
+        c1 = n1;
+        c2 = n2;
+        csc = nsc;
+        cd = nd;
+      }
+    }
+    // partial of this wave: C layout row = 4 kq + r, column nl
+    float* slot = part + size_t(it & 1) * (kQ6kWaves * 256);
+#pragma unroll
+    for (int r = 0; r < 4; r++) slot[wave * 256 + (4 * kq + r) * 16 + nl] = acc[r];
+    __syncthreads();
+    if (wave == (it & (kQ6kWaves - 1))) {
+      const int row = lane >> 2, n0 = 4 * (lane & 3);
+      float v[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+      for (int w = 0; w < kQ6kWaves; w++) {  // wave order; four reads in flight (sixteen would spill)
+        const float4 pv = *reinterpret_cast<const float4*>(slot + w * 256 + row * 16 + n0);
+        v[0] += pv.x;
+        v[1] += pv.y;
+        v[2] += pv.z;
+        v[3] += pv.w;
+      }
+      int orow = row;
+      bool valid = row < mloc;
+      if constexpr (HILO) {  // rows 2 i (hi) and 2 i + 1 (lo) sit four lanes apart
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+          const float other = __shfl_xor(v[e], 4);
+          v[e] = (row & 1) ? other + v[e] : v[e] + other;
+        }
+        orow = row >> 1;
+        valid = (row & 1) == 0 && orow < mloc;
+      }
+      if (valid && s * 16 + n0 < W.n) gemm_epilogue4(a, row0 + orow, s * 16 + n0, v);
+    }
+  }
+}
+
+bool q6k_gemv_geometry(int m, int k, int ns, int act_t, int cus, Q6kGemvGeom* g) {
+  const size_t row_bytes = size_t(k) * 2;
+  const int per = act_t == kActF16 ? 1 : 2;  // fp16 rows in LDS per activation row
+  int cap = int(std::min<size_t>((kQ6kLdsMax - kQ6kPartBytes) / row_bytes, 16)) / per;
+  if (cap < 1) return false;
+  g->rows_pp = std::min(m, cap);
+  g->passes = (m + g->rows_pp - 1) / g->rows_pp;
+  g->grid = std::max(1, std::min(ns, cus));
+  g->waves = kQ6kWaves;
+  g->lds = size_t(g->rows_pp) * per * row_bytes + kQ6kPartBytes;
+  return true;
+}
+
+template <auto K>
+static hipError_t q6k_launch_lds(dim3 g, dim3 b, size_t lds, hipStream_t st, const Q6kGemvArgs& args) {
+  static bool attr_set = false;  // opt the kernel in to > 64 KiB of dynamic LDS once
+  if (!attr_set) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       int(kQ6kLdsMax));
+    if (e != hipSuccess) return e;
+    attr_set = true;
+  }
+  hipLaunchKernelGGL(K, g, b, lds, st, args);
+  return hipGetLastError();
+}
+
+hipError_t launch_q6k_gemv(const GemmArgs& a, int act_t, const Q6kGemvGeom& g, hipStream_t st) {
+  if (a.M < 1 || a.M > 16 || a.K % 256 != 0 || g.lds > kQ6kLdsMax || g.rows_pp < 1) return hipErrorInvalidValue;
+  Q6kGemvArgs qa{a, g.rows_pp};
+  const dim3 grid(g.grid, g.passes), block(kQ6kWaves * 64);
+  if (act_t == kActF32) return q6k_launch_lds<woq_q6k_gemv_kernel<kActF32>>(grid, block, g.lds, st, qa);
+  if (act_t == kActF16) return q6k_launch_lds<woq_q6k_gemv_kernel<kActF16>>(grid, block, g.lds, st, qa);
+  return q6k_launch_lds<woq_q6k_gemv_kernel<kActBF16>>(grid, block, g.lds, st, qa);
+}
+
+// ------------------------------------------------------------------------------------------------ GEMM, M > 16
+// Register-staged MFMA tile kernel in the manner of woq_gemm_kernel (woq_kernels.hip): a 128 x 128 output tile per
+// workgroup, 8 waves as 4 (M) x 2 (N), a wave 32 rows x 4 stripes; the K step is half a superblock (128).  A goes
+// through LDS as fp16 (16-B chunks XOR-swizzled by the row); the quants of the wave's four stripes are loaded a step
+// ahead.  A lane's low-nibble dword holds two groups (woq_layout.h), which is one v_mfma_f32_16x16x32_f16: the B
+// fragment is fp16(sc * q) -- q exact, sc an fp16 integer, the product rounded once -- and the lane's A fragment the
+// matching two runs of four k.  acc_sb collects a superblock, acc += d * acc_sb in fp32.
+template <int AT>
+__global__ __launch_bounds__(512) void woq_q6k_gemm_kernel(GemmArgs a) {
+  constexpr int KT = 128, BM = 128, ROWB = KT * 2, CHUNKS = ROWB / 16;
+  __shared__ __attribute__((aligned(16))) char lds_a[BM * ROWB];
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave-uniform: scalar
+  const int wm = wave >> 1, wn = wave & 1;
+  const int nl = lane & 15, kq = lane >> 4;
+  const SkinnyWeight& W = a.w;
+  const int nbm = (a.M + BM - 1) / BM;
+  const int bn = blockIdx.x / nbm, bm = blockIdx.x % nbm;
+  const int m0 = bm * BM;
+  const int s0 = bn * 8 + wn * 4;
+  const int nsb = W.nt;
+
+  f4_t acc[2][4], accsb[2][4];
+#pragma unroll
+  for (int i = 0; i < 2; i++)
+#pragma unroll
+    for (int j = 0; j < 4; j++) acc[i][j] = accsb[i][j] = f4_t{0.f, 0.f, 0.f, 0.f};
+
+  const int ch = threadIdx.x % CHUNKS;  // 16 chunks of 8 k; 32 rows per pass, 4 passes
+  const int r0 = threadIdx.x / CHUNKS;
+  const bool vec_ok = a.vec_ok != 0;
+  const u4_t* qp = static_cast<const u4_t*>(W.tiles);
+  const u4_t* scp = reinterpret_cast<const u4_t*>(W.zps);
+  const _Float16* dp = static_cast<const _Float16*>(W.scales);
+  const h2_t m1056 = h2_splat(-1056.f);
+
+  size_t sbi[4];  // (stripe, superblock 0) index of the wave's stripes, clamped to the last stripe
+#pragma unroll
+  for (int j = 0; j < 4; j++) sbi[j] = size_t(min(s0 + j, W.ns - 1)) * nsb;
+  u4_t lo[4], hi[4], sc[4], lo_n[4];
+#pragma unroll
+  for (int j = 0; j < 4; j++) lo[j] = qp[sbi[j] * 192 + lane];
+
+  const int nsteps = nsb * 2;
+  for (int t = 0; t < nsteps; t++) {
+    const int b = t >> 1, half = t & 1;
+#pragma unroll
+    for (int p = 0; p < 4; p++) {
+      const int r = r0 + p * 32;
+      const int row = m0 + r;
+      float v[8];
+      if (row < a.M) {
+        load_a8<AT>(a.A, a.lda, row, t * KT + ch * 8, a.K, nullptr, vec_ok, v);
+      } else {
+#pragma unroll
+        for (int j = 0; j < 8; j++) v[j] = 0.f;
+      }
+      h8_t hv;
+#pragma unroll
+      for (int j = 0; j < 8; j++) hv[j] = _Float16(v[j]);
+      *reinterpret_cast<h8_t*>(lds_a + r * ROWB + (ch ^ (r & 15)) * 16) = hv;
+    }
+    if (half == 0) {  // the superblock's crumbs and sub-scales
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        hi[j] = qp[(sbi[j] + b) * 192 + 128 + lane];
+        sc[j] = scp[(sbi[j] + b) * 16 + nl];
+      }
+    }
+    if (t + 1 < nsteps) {
+#pragma unroll
+      for (int j = 0; j < 4; j++) lo_n[j] = qp[(sbi[j] + ((t + 1) >> 1)) * 192 + ((t + 1) & 1) * 64 + lane];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int dd = 0; dd < 4; dd++) {
+      // groups g0 = 8 half + 2 dd and g0 + 1 of the superblock: pairs 0, 1 / 2, 3 of the dword
+      h8_t bf[4];
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        const uint32_t lw = lo[j][dd];
+        const uint32_t hw = (half ? (dd < 2 ? hi[j][2] : hi[j][3]) : (dd < 2 ? hi[j][0] : hi[j][1])) >> (8 * (dd & 1));
+        const int g0 = 8 * half + 2 * dd;
+        const h2_t s0h = h2_splat(float(q6k_sc(sc[j], g0))), s1h = h2_splat(float(q6k_sc(sc[j], g0 + 1)));
+        const h2_t p0 = q6k_pair(lw, q6k_hi_at4<0>(hw), m1056) * s0h;
+        const h2_t p1 = q6k_pair(lw >> 4, q6k_hi_at4<1>(hw), m1056) * s0h;
+        const h2_t p2 = q6k_pair(lw >> 8, q6k_hi_at4<2>(hw), m1056) * s1h;
+        const h2_t p3 = q6k_pair(lw >> 12, q6k_hi_at4<3>(hw), m1056) * s1h;
+        bf[j] = h8_t{p0[0], p0[1], p1[0], p1[1], p2[0], p2[1], p3[0], p3[1]};
+      }
+#pragma unroll
+      for (int i = 0; i < 2; i++) {
+        const int r = wm * 32 + i * 16 + nl;
+        // k (local) = 32 dd + 4 kq + e and + 16: chunks 4 dd + (kq >> 1) and + 2, byte (kq & 1) * 8 inside
+        const char* rp = lds_a + r * ROWB + (kq & 1) * 8;
+        const h4_t a0 = *reinterpret_cast<const h4_t*>(rp + ((4 * dd + (kq >> 1)) ^ (r & 15)) * 16);
+        const h4_t a1 = *reinterpret_cast<const h4_t*>(rp + ((4 * dd + 2 + (kq >> 1)) ^ (r & 15)) * 16);
+        const h8_t af{a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+          accsb[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af, bf[j], accsb[i][j], 0, 0, 0);
+      }
+    }
+    if (half == 1) {
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        const float d = float(dp[(sbi[j] + b) * 16 + nl]);
+#pragma unroll
+        for (int i = 0; i < 2; i++) {
+#pragma unroll
+          for (int r = 0; r < 4; r++) acc[i][j][r] = __builtin_fmaf(d, accsb[i][j][r], acc[i][j][r]);
+          accsb[i][j] = f4_t{0.f, 0.f, 0.f, 0.f};
+        }
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < 4; j++) lo[j] = lo_n[j];
+  }
+
+  // C layout: column nl, rows 4 kq + r.  gemm_epilogue4 takes four consecutive columns of a row, so the 16 x 16 tile
+  // is turned through LDS (the A tile is free after the last barrier): wave-private 1 KiB per tile
+  float* tbuf = reinterpret_cast<float*>(lds_a) + wave * 256;
+#pragma unroll
+  for (int j = 0; j < 4; j++) {
+    if (s0 + j >= W.ns) continue;
+#pragma unroll
+    for (int i = 0; i < 2; i++) {
+#pragma unroll
+      for (int r = 0; r < 4; r++) tbuf[(4 * kq + r) * 16 + nl] = acc[i][j][r];
+      __builtin_amdgcn_wave_barrier();
+      const int trow = lane >> 2, n0 = (s0 + j) * 16 + 4 * (lane & 3);
+      const float4 pv = *reinterpret_cast<const float4*>(tbuf + trow * 16 + 4 * (lane & 3));
+      float v[4] = {pv.x, pv.y, pv.z, pv.w};
+      const int row = m0 + wm * 32 + i * 16 + trow;
+      if (row < a.M && n0 < W.n) gemm_epilogue4(a, row, n0, v);
+      __builtin_amdgcn_wave_barrier();
+    }
+  }
+}
+
+hipError_t launch_q6k_gemm(const GemmArgs& a, int act_t, hipStream_t st) {
+  if (a.K % 256 != 0) return hipErrorInvalidValue;
+  const dim3 grid(((a.M + 127) / 128) * ((a.w.ns + 7) / 8));
+  if (act_t == kActF32)
+    hipLaunchKernelGGL(woq_q6k_gemm_kernel<kActF32>, grid, dim3(512), 0, st, a);
+  else if (act_t == kActF16)
+    hipLaunchKernelGGL(woq_q6k_gemm_kernel<kActF16>, grid, dim3(512), 0, st, a);
+  else
+    hipLaunchKernelGGL(woq_q6k_gemm_kernel<kActBF16>, grid, dim3(512), 0, st, a);
+  return hipGetLastError();
+}
+
+}  // namespace nad
