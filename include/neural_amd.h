@@ -195,6 +195,13 @@ int nad_plan_forward(int bits, int n, int k, int blocksize, int scale_t, int asy
                      int nout);
 /* the same dry run for a loaded device weight (its format, act-order, fold range and compute mode included) */
 int nad_plan_weight(const void* devstor, int m, int act_dtype, int64_t* out, int nout);
+/* Dry runs of nad_device_qkv_forward, for three weight geometries of one format (nq, nk, nv columns; no GPU needed) and
+ * for three loaded weights.  out as nad_plan_forward's: the kernel, grid, threads, split-K runs and flags are those of
+ * the last main launch, `launches` counts every launch of the call -- a fused gemm7 prefill shows one main launch whose
+ * grid covers the column tiles of all three weights, the separate form (NAD_GEMM7_FUSE=0) two launches more. */
+int nad_plan_qkv_forward(int bits, int nq, int nk, int nv, int k, int blocksize, int scale_t, int asym, int m,
+                         int act_dtype, int64_t* out, int nout);
+int nad_plan_qkv(const void* wq, const void* wk, const void* wv, int m, int act_dtype, int64_t* out, int nout);
 /* fused Q/K/V (ip_fusion_qkv.cpp:22-93): out_i = X . W_i^T, one launch; W_i share K, blocksize, bits, scale dtype */
 int nad_device_qkv_forward(const void* act, int act_dtype, const void* wq, const void* wk, const void* wv, float* oq,
                            float* ok, float* ov, int m, int k, int lda, int ldo_q, int ldo_k, int ldo_v, void* queue);

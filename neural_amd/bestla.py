@@ -181,8 +181,32 @@ def plan_forward(bits, n, k, group_size=128, scale_dtype="fp16", asym=False, m=1
     r = lib().nad_plan_forward(bits, n, k, group_size, st, int(asym), m, at, _ptr(o), 6)
     if r != 6:
         raise RuntimeError(f"nad_plan_forward failed: {last_error()}")
+    return _plan_dict(o)
+
+
+def _plan_dict(o):
     return dict(kernel=KERNELS.get(int(o[0]), str(int(o[0]))), grid=int(o[1]), threads=int(o[2]), ksplit=int(o[3]),
                 fold=bool(o[4] & 1), ksw=bool(o[4] & 2), m1_spec=bool(o[4] & 4), launches=int(o[5]))
+
+
+def plan_qkv_forward(bits, nq, nk, nv, k, group_size=128, scale_dtype="fp16", asym=False, m=1, act="fp32"):
+    """What a fused Q/K/V forward of three weights of this format launches (nad_plan_qkv_forward: no GPU needed): the
+    last main launch's kernel, grid, threads, ksplit and flags; `launches` counts every launch of the call."""
+    o = np.zeros(6, np.int64)
+    st = {"fp32": 0, "bf16": 1, "fp16": 2}[scale_dtype]
+    at = {"fp32": 0, "fp16": 1, "bf16": 2}[act]
+    if lib().nad_plan_qkv_forward(bits, nq, nk, nv, k, group_size, st, int(asym), m, at, _ptr(o), 6) != 6:
+        raise RuntimeError(f"nad_plan_qkv_forward failed: {last_error()}")
+    return _plan_dict(o)
+
+
+def plan_qkv(wq, wk, wv, m, act="fp32"):
+    """The same dry run for three loaded DeviceWeights (nad_plan_qkv)."""
+    o = np.zeros(6, np.int64)
+    at = {"fp32": 0, "fp16": 1, "bf16": 2}[act]
+    if lib().nad_plan_qkv(wq.desc, wk.desc, wv.desc, m, at, _ptr(o), 6) != 6:
+        raise RuntimeError(f"nad_plan_qkv failed: {last_error()}")
+    return _plan_dict(o)
 
 
 def _torch():
@@ -324,8 +348,7 @@ class DeviceWeight:
         at = {"fp32": 0, "fp16": 1, "bf16": 2}[act]
         if lib().nad_plan_weight(self.desc, m, at, _ptr(o), 6) != 6:
             raise RuntimeError(f"nad_plan_weight failed: {last_error()}")
-        return dict(kernel=KERNELS.get(int(o[0]), str(int(o[0]))), grid=int(o[1]), threads=int(o[2]),
-                    ksplit=int(o[3]), fold=bool(o[4] & 1), ksw=bool(o[4] & 2), m1_spec=bool(o[4] & 4), launches=int(o[5]))
+        return _plan_dict(o)
 
     def set_compute(self, mode):
         """Per-weight arithmetic (nad_device_set_compute): None / -1 follow the thread / process mode, COMPUTE_FP or

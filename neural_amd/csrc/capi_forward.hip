@@ -962,6 +962,57 @@ extern "C" int nad_device_qkv_forward(const void* act, int act_dtype, const void
   return 0;
 }
 
+// Dry run of nad_device_qkv_forward: every launch on that path goes through planned(), so the pointers are never
+// dereferenced.  The record is nad_plan_forward's: the last main launch, and all launches counted.
+static int plan_qkv_for(const DeviceWeight* const ws[3], int m, int act_dtype, int64_t* out, int nout) {
+  if (!out || nout < 0 || m <= 0) {
+    set_err("nad_plan_qkv*: bad arguments (m=%d)", m);
+    return -1;
+  }
+  NadPlan plan;
+  set_plan(&plan);
+  const void* act = reinterpret_cast<const void*>(uintptr_t(1) << 42);  // aligned, never dereferenced on the host
+  float* y[3];
+  for (int i = 0; i < 3; i++) y[i] = reinterpret_cast<float*>((uintptr_t(1) << 43) + (uintptr_t(i) << 38));
+  const int k = ws[0]->k;
+  const int rc = nad_device_qkv_forward(act, act_dtype, ws[0], ws[1], ws[2], y[0], y[1], y[2], m, k, k, ws[0]->n,
+                                        ws[1]->n, ws[2]->n, nullptr);
+  set_plan(nullptr);
+  if (rc) return -1;
+  const int64_t v[6] = {plan.kernel, plan.grid, plan.block, plan.ksplit, plan.fold, plan.launches};
+  const int c = nout < 6 ? nout : 6;
+  std::memcpy(out, v, sizeof(int64_t) * size_t(c));
+  return c;
+}
+
+extern "C" int nad_plan_qkv_forward(int bits, int nq, int nk, int nv, int k, int blocksize, int scale_t, int asym,
+                                    int m, int act_dtype, int64_t* out, int nout) {
+  if ((bits != 2 && bits != 4 && bits != 8) || nq <= 0 || nk <= 0 || nv <= 0 || k <= 0) {
+    set_err("nad_plan_qkv_forward: bad arguments (bits=%d n=%d,%d,%d k=%d)", bits, nq, nk, nv, k);
+    return -1;
+  }
+  if (blocksize <= 0) blocksize = k;
+  const int ns[3] = {nq, nk, nv};
+  DeviceWeight w[3] = {};
+  const DeviceWeight* ws[3];
+  for (int i = 0; i < 3; i++) {
+    layout_geometry(w[i], bits, ns[i], k, blocksize, scale_t, asym != 0, false, false);
+    layout_assign(w[i], reinterpret_cast<void*>((uintptr_t(1) << 41) + (uintptr_t(i) << 38)));  // never dereferenced
+    w[i].f4kind = -1;
+    w[i].fold_ok = 1;
+    w[i].owner = nullptr;
+    ws[i] = &w[i];
+  }
+  return plan_qkv_for(ws, m, act_dtype, out, nout);
+}
+
+extern "C" int nad_plan_qkv(const void* wq, const void* wk, const void* wv, int m, int act_dtype, int64_t* out,
+                            int nout) {
+  const DeviceWeight* ws[3] = {as_weight(wq), as_weight(wk), as_weight(wv)};
+  if (!ws[0] || !ws[1] || !ws[2]) return -1;
+  return plan_qkv_for(ws, m, act_dtype, out, nout);
+}
+
 // ------------------------------------------------------------------------------------------------ fused FFN
 // The gate/up half of the fused FFN (ip_fusion_ffn.cpp:407-433): tmp2 = act(X.W1^T) * (X.W3^T), tmp1 = act(X.W1^T)
 // (optional at M <= 16, required above).  Decode: one dual-weight stream launch; prefill: two GEMM launches.

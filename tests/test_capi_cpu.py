@@ -255,6 +255,40 @@ def test_plan_forward_kernel_choice():
     assert p(8, 4096, 4096, 128, m=2048)["fold"] and p(2, 4096, 4096, 128, m=2048)["fold"]
 
 
+def test_plan_qkv_forward_records_every_launch(knob):
+    """nad_plan_qkv_forward: the fused Q/K/V entry as a dry run.  There is no GPU here, so a launch on that path that
+    did not go through the recorder would fail the call: every M range of int4 g128 and int2 g64 plans cleanly, on the
+    kernel the single-weight plan names.  The fused gemm7 prefill (int4 g128, N = 3 x 4096, K = 4096, M = 2048: 256-row
+    tiles, whole K) is ONE main launch over 8 row tiles x 96 column tiles; NAD_GEMM7_FUSE=0 makes it three of 8 x 32."""
+    q = bestla.plan_qkv_forward
+    for bits, g in ((4, 128), (2, 64)):
+        for m in (1, 5, 40, 130, 2048):
+            for act in ("fp32", "fp16"):
+                r = q(bits, 4096, 4096, 4096, 4096, g, m=m, act=act)
+                one = bestla.plan_forward(bits, 4096, 4096, g, m=m, act=act)
+                assert r["launches"] >= 1 and r["threads"] > 0, (bits, m, act, r)
+                if m > 16:  # above the decode range the fused entry runs each weight's own kernel, or gemm7 fused
+                    assert r["kernel"] == one["kernel"], (bits, m, act, r, one)
+                else:       # one stream launch over the three weights
+                    assert r["kernel"] in ("woq_gemv_m1_kernel", "woq_gemv_kernel") and r["launches"] == 1, (m, r)
+    r = q(4, 1024, 1024, 4096, 4096, 128, m=1)      # unequal N plan as well
+    assert r["kernel"] == "woq_gemv_m1_kernel", r
+    for act, pre in (("fp16", 0), ("fp32", 1)):      # fp32 rows: one conversion pass ahead of the GEMMs
+        knob("NAD_GEMM7_FUSE", None)
+        r = q(4, 4096, 4096, 4096, 4096, 128, m=2048, act=act)
+        assert (r["kernel"], r["grid"], r["ksplit"], r["fold"], r["launches"]) == \
+            ("woq_gemm7_kernel", 8 * 96, 1, True, pre + 1), r
+        knob("NAD_GEMM7_FUSE", "0")
+        r = q(4, 4096, 4096, 4096, 4096, 128, m=2048, act=act)
+        assert (r["kernel"], r["grid"], r["ksplit"], r["launches"]) == ("woq_gemm7_kernel", 8 * 32, 1, pre + 3), r
+    knob("NAD_GEMM7_FUSE", None)
+    # asymmetric weights and bf16 scales fuse too; int2 never does (the fused instantiation is int4 g128 * 2^j)
+    assert q(4, 4096, 3072, 3072, 4096, 128, "bf16", True, m=2048, act="fp16")["grid"] == 8 * (32 + 24 + 24)
+    assert q(2, 4096, 4096, 4096, 4096, 64, m=2048, act="fp16")["launches"] == 3
+    with pytest.raises(RuntimeError):
+        q(3, 64, 64, 64, 256, 32, m=1)
+
+
 def test_plan_mid_keeps_whole_4_stripe_geometry(knob):
     """The mid-M kernel's automatic 8-stripe form (NAD_MID_WIDE=2) is dropped where its grid does not fit the CUs either:
     int4 g64, N = 40960, K = 4096, M = 32 gives 640 x 1 workgroups of 4 stripes and 320 > 256 of 8.  The geometry that

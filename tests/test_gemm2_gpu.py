@@ -144,8 +144,17 @@ def test_gemm7_fused_qkv_is_the_separate_launches(oracle, knob, m, ns, asym):
     blobs = [_blob(oracle, n, k, 128, S4, BF16 if asym else F16, asym, 4, seed=70 + i) for i, n in enumerate(ns)]
     ws = [bestla.DeviceWeight(b) for b in blobs]
     x = (torch.rand((m, k), device="cuda") - 0.5)
+    # the fused launch is taken (else both sides below are the separate launches): the conversion of the fp32 rows and
+    # ONE gemm7 launch over the column tiles of all three weights, at one of the fused kernel's tile heights
+    tiles = [-(-n // 128) for n in ns]
+    plan = bestla.plan_qkv(*ws, m, "fp32")
+    assert (plan["kernel"], plan["ksplit"], plan["launches"]) == ("woq_gemm7_kernel", 1, 2), plan
+    assert plan["grid"] in [-(-m // bm) * sum(tiles) for bm in (64, 128, 256)], plan
     ys = [y.cpu().numpy() for y in bestla.qkv_forward(x, *ws)]
     knob("NAD_GEMM7_FUSE", "0")
+    sep = bestla.plan_qkv(*ws, m, "fp32")
+    assert (sep["kernel"], sep["ksplit"], sep["launches"]) == ("woq_gemm7_kernel", 1, 4), sep
+    assert sep["grid"] * sum(tiles) == plan["grid"] * tiles[2], (sep, plan)  # the last weight's own tiles, same height
     y0 = [y.cpu().numpy() for y in bestla.qkv_forward(x, *ws)]
     for a, b in zip(ys, y0):
         assert np.array_equal(a, b)
