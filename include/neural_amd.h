@@ -191,6 +191,7 @@ int nad_device_forward(const void* act, int act_dtype, const void* devstor, floa
 #define NAD_KERNEL_MID 10      /* woq_mid_kernel: 12 (fp16) / 8 (fp32, bf16) <= M <= 64, int4 / int2 */
 #define NAD_KERNEL_Q6K_GEMV 11 /* woq_q6k_gemv_kernel: GGUF Q6_K, M <= 16 (sub-scales in fp32: flags bit 0 clear) */
 #define NAD_KERNEL_Q6K_GEMM 12 /* woq_q6k_gemm_kernel: GGUF Q6_K, M > 16 (sc * q folded into fp16: flags bit 0 set) */
+#define NAD_KERNEL_Q6K_I8 13   /* woq_q6k_i8_kernel: GGUF Q6_K in mode NAD_COMPUTE_Q8_K, any M (flags bit 0 clear) */
 int nad_plan_forward(int bits, int n, int k, int blocksize, int scale_t, int asym, int m, int act_dtype, int64_t* out,
                      int nout);
 /* the same dry run for a loaded device weight (its format, act-order, fold range and compute mode included) */
@@ -255,10 +256,17 @@ int nad_get_compute_mode(void);
 int nad_set_thread_compute_mode(int mode);
 /* per-weight arithmetic, as the reference selects it per blob core (bestla_gemm.cpp:516-616): -1 follow the
  * thread / process mode, 0 fp, 1 int8 (integer-core blobs and the legacy GGUF block types; other weights -- NFloat
- * weights and GGUF Q6_K among them -- stay fp: the call succeeds and nad_device_get_compute keeps returning 0).  Takes
- * precedence over both; a fused call whose weights resolve to different arithmetic runs each weight in its own. */
+ * weights and GGUF Q6_K among them -- stay fp: the call succeeds and nad_device_get_compute keeps returning 0), or
+ * NAD_COMPUTE_Q8_K for a GGUF Q6_K weight: the reference's arithmetic for the type (quantize_fns, ne_layers.c:322-326)
+ * -- every activation row quantized to block_q8_K, ggml_vec_dot_q6_K_q8_K's integer dot product per superblock --
+ * on woq_q6k_i8_kernel at every M.  Mode 2 on any other weight returns -1 and leaves its mode unchanged; the thread
+ * and process modes keep their two values, so a Q6_K weight never follows them into integer arithmetic.  The weight's
+ * own mode takes precedence over both; a fused call whose weights resolve to different arithmetic runs each weight in
+ * its own. */
+#define NAD_COMPUTE_Q8_K 2
 int nad_device_set_compute(void* devstor, int mode);
-/* the arithmetic a forward of this weight takes now: 0 fp, 1 int8, -1 not a device weight */
+/* the arithmetic a forward of this weight takes now: 0 fp, 1 int8, 2 Q8_K (a Q6_K weight set to it), -1 not a device
+ * weight */
 int nad_device_get_compute(const void* devstor);
 /* kernel::wrapper::QuantizeU8ColBlock::forward (kernel_wrapper.h:571-590) on device pointers: act [m][lda] in
  * act_dtype, q [m][ldq] u8, scales / zps [m][ld_scale] per block, blkreduce (may be NULL) = sum(round(x/s)) * s. */
@@ -311,7 +319,12 @@ int nad_gguf_device_load(int type, const void* blocks, int n, int k, void* devst
  * nad_device_* / bestla_device_* forward accepts the descriptor with every single-weight epilogue;
  * nad_device_qkv_forward runs the three weights one after another when any is Q6_K; nad_device_ffn_gate_up /
  * nad_device_ffn_forward run gate and up as two passes then, and the partner may be of any format.  Arithmetic is fp
- * only (nad_device_set_compute(w, 1) leaves it fp: the reference's Q8_K integer dot product is not reproduced);
+ * by default and under every process / thread mode (nad_device_set_compute(w, 1) leaves it fp);
+ * nad_device_set_compute(w, NAD_COMPUTE_Q8_K) switches the weight to the reference's Q8_K integer arithmetic: per
+ * (row r, superblock b) isum = sum_g sc[g] * sum_i q[16 g + i] * a[16 g + i] exact in int32 on
+ * v_mfma_i32_16x16x64_i8, y = sum_b fp32(fp32(d_w[b]) * d_a[r][b]) * float(isum_b) in fp32 (each wave its superblocks
+ * b = wave, wave + 16, ... in ascending order, then the 16 waves in wave order), the rows quantized inside the kernel
+ * (one launch at every M, through every entry above).
  * nad_batch_create refuses a Q6_K weight.  nad_device_unpack_fp32 returns (d * sc) * q, bit for bit
  * dequantize_row_q6_K (vectors/cpu/quantize.h:956-999). */
 #define NAD_GGUF_Q6_K 14
@@ -321,6 +334,12 @@ int nad_q6_k_device_load(const void* blocks, int n, int k, void* devstor, void* 
 /* quantize_row_q8_1_reference (vectors/cpu/quantize.h:546-579) on device pointers: act [m][lda] -> m rows of K/32
  * blocks {float d; float s; int8 qs[32]} */
 int nad_quant_q8_1(const void* act, int act_dtype, int m, int k, int lda, void* blocks, void* queue);
+/* quantize_row_q8_K_reference (vectors/cpu/quantize.h:1020-1055) on device pointers: act [m][lda] in act_dtype
+ * -> m rows of k/256 blocks {float d; int8 qs[256]; int16 bsums[16]} (292 bytes); k % 256 == 0.  Bit for bit the
+ * reference for finite inputs whose per-superblock largest magnitude is zero or an fp32 normal; an all-zero superblock
+ * gets d = 0, codes 0 and bsums 0 (the reference leaves bsums unwritten there).  Bad arguments: -1 before anything on
+ * the device is touched. */
+int nad_quant_q8_k(const void* act, int act_dtype, int m, int k, int lda, void* blocks, void* queue);
 /* host convenience: (re)pack one blob into fp32 dequantized [K][N] from the device tile layout (round-trip check) */
 int nad_device_unpack_fp32(const void* devstor, float* host_out, void* queue);
 

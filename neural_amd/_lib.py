@@ -98,6 +98,7 @@ SIGNATURES = {
     "nad_gguf_device_size": (_sz, [_i, _i, _i]),
     "nad_gguf_device_load": (_i, [_i, _p, _i, _i, _p, _p, _sz, _p]),
     "nad_quant_q8_1": (_i, [_p, _i, _i, _i, _i, _p, _p]),
+    "nad_quant_q8_k": (_i, [_p, _i, _i, _i, _i, _p, _p]),
     "nad_q6_k_device_size": (_sz, [_i, _i]),
     "nad_q6_k_device_load": (_i, [_p, _i, _i, _p, _p, _sz, _p]),
     "nad_batch_create": (_p, [_p, _i]),

@@ -169,7 +169,8 @@ def split_range(blob, axis, rank, world, unit=1):
 # ---------------------------------------------------------------------------------------------------- device
 KERNELS = {1: "woq_gemv_m1_kernel", 2: "woq_gemv_kernel", 3: "woq_skinny_kernel", 4: "woq_i8_kernel",
            5: "woq_gemm3_kernel", 6: "woq_gemm4_kernel", 7: "woq_gemm2_kernel", 8: "woq_gemm_kernel",
-           9: "woq_gemm7_kernel", 10: "woq_mid_kernel", 11: "woq_q6k_gemv_kernel", 12: "woq_q6k_gemm_kernel"}
+           9: "woq_gemm7_kernel", 10: "woq_mid_kernel", 11: "woq_q6k_gemv_kernel", 12: "woq_q6k_gemm_kernel",
+           13: "woq_q6k_i8_kernel"}
 
 
 def plan_forward(bits, n, k, group_size=128, scale_dtype="fp16", asym=False, m=1, act="fp32"):
@@ -351,14 +352,16 @@ class DeviceWeight:
         return _plan_dict(o)
 
     def set_compute(self, mode):
-        """Per-weight arithmetic (nad_device_set_compute): None / -1 follow the thread / process mode, COMPUTE_FP or
-        COMPUTE_INT8 (integer-core blobs and GGUF matrices only; other weights stay fp)."""
+        """Per-weight arithmetic (nad_device_set_compute): None / -1 follow the thread / process mode, COMPUTE_FP,
+        COMPUTE_INT8 (integer-core blobs and the legacy GGUF block types only; other weights stay fp) or COMPUTE_Q8_K
+        (a GGUF Q6_K weight only -- any other weight raises and keeps its mode: the reference's Q8_K activation rows
+        and integer dot product, woq_q6k_i8_kernel at every M)."""
         check(lib().nad_device_set_compute(self.desc, -1 if mode is None else int(mode)), "nad_device_set_compute")
         return self
 
     @property
     def compute(self):
-        """the arithmetic a forward takes now: COMPUTE_FP or COMPUTE_INT8"""
+        """the arithmetic a forward takes now: COMPUTE_FP, COMPUTE_INT8 or COMPUTE_Q8_K"""
         return lib().nad_device_get_compute(self.desc)
 
     def unpack(self, stream=None):
@@ -369,6 +372,7 @@ class DeviceWeight:
 
 
 COMPUTE_FP, COMPUTE_INT8 = 0, 1
+COMPUTE_Q8_K = 2  # a GGUF Q6_K weight's own mode (DeviceWeight.set_compute): the reference's Q8_K integer arithmetic
 # GGUF block types (the reference's ne_type values, neural_speed/core/data_types.h)
 GGUF_Q4_0, GGUF_Q4_1, GGUF_Q5_0, GGUF_Q5_1, GGUF_Q8_0 = 2, 3, 6, 7, 8
 GGUF_Q6_K = 14  # superblocks of 256 (DeviceWeight.from_q6_k; from_gguf routes it there)
@@ -423,6 +427,16 @@ def quant_q8_1(x, stream=None):
     m, k = x.shape
     out = torch.empty((m, k // 32 * 40), dtype=torch.uint8, device=x.device)
     check(lib().nad_quant_q8_1(_ptr(x), _act_code(x), m, k, x.stride(0), _ptr(out), _stream(stream)), "nad_quant_q8_1")
+    return out
+
+
+def quant_q8_k(x, stream=None):
+    """quantize_row_q8_K_reference (vectors/cpu/quantize.h:1020-1055) on the GPU: x cuda [M][K], K % 256 == 0 -> uint8
+    [M][K/256 * 292] blocks {float d; int8 qs[256]; int16 bsums[16]}"""
+    torch = _torch()
+    m, k = x.shape
+    out = torch.empty((m, k // 256 * 292), dtype=torch.uint8, device=x.device)
+    check(lib().nad_quant_q8_k(_ptr(x), _act_code(x), m, k, x.stride(0), _ptr(out), _stream(stream)), "nad_quant_q8_k")
     return out
 
 

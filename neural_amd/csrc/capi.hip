@@ -258,6 +258,10 @@ static int effective_mode(const DeviceWeight& w) { return w.compute > 0 ? w.comp
 bool int8_compute(const DeviceWeight& w) {
   return effective_mode(w) == 1 && (w.reduce != nullptr || gguf_type(w) != 0);
 }
+// Mode 2 (NAD_COMPUTE_Q8_K) is a GGUF Q6_K weight's own setting only: the reference's Q8_K activation rows and
+// ggml_vec_dot_q6_K_q8_K integer dot product (woq_q6k_i8_kernel).  The thread and process modes keep their two values,
+// so a Q6_K weight never follows them into integer arithmetic.
+bool q8k_compute(const DeviceWeight& w) { return is_q6k(w) && w.compute == NAD_COMPUTE_Q8_K + 1; }
 
 extern "C" int nad_set_compute_mode(int mode) {
   if (mode != 0 && mode != 1) {
@@ -282,19 +286,26 @@ extern "C" int nad_device_set_compute(void* devstor, int mode) {
     set_err("nad_device_set_compute: not a device weight");
     return -1;
   }
-  if (mode < -1 || mode > 1) {
-    set_err("weight compute mode must be -1 (follow the thread/process setting), 0 (fp) or 1 (int8), got %d", mode);
+  if (mode < -1 || mode > NAD_COMPUTE_Q8_K) {
+    set_err("weight compute mode must be -1 (follow the thread/process setting), 0 (fp), 1 (int8) or 2 (Q8_K, GGUF "
+            "Q6_K weights only), got %d", mode);
+    return -1;
+  }
+  if (mode == NAD_COMPUTE_Q8_K && !is_q6k(*w)) {
+    set_err("weight compute mode 2 (Q8_K integer arithmetic) is for GGUF Q6_K weights only; this weight has bits = %d",
+            w->bits);
     return -1;
   }
   w->compute = mode + 1;
   return 0;
 }
-// the arithmetic a forward of this weight takes right now: 0 fp, 1 int8
+// the arithmetic a forward of this weight takes right now: 0 fp, 1 int8, 2 Q8_K (a Q6_K weight set to it)
 extern "C" int nad_device_get_compute(const void* devstor) {
   const DeviceWeight* w = static_cast<const DeviceWeight*>(devstor);
   if (!w || w->magic != kWeightMagic) {
     set_err("nad_device_get_compute: not a device weight");
     return -1;
   }
+  if (q8k_compute(*w)) return NAD_COMPUTE_Q8_K;
   return int8_compute(*w) ? 1 : 0;
 }

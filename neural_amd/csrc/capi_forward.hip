@@ -716,7 +716,9 @@ static int forward_min(const Act& x, const DeviceWeight& w, const Out& o, const 
 }
 // A GGUF Q6_K weight (woq_q6k.hip): the decode GEMV up to 16 rows -- sub-scales applied in fp32, plan fold 0 -- and the
 // register-staged GEMM above, which folds sc * q into its fp16 fragments (plan fold 1).  Both apply the epilogue
-// themselves (gemm_epilogue4: every single-weight kind and the multiply by aux of the FFN's second pass).
+// themselves (gemm_epilogue4: every single-weight kind and the multiply by aux of the FFN's second pass).  A weight
+// in mode 2 (q8k_compute) takes woq_q6k_i8_kernel at every M instead: Q8_K activation rows quantized in the kernel's own
+// staging (no pre-pass, one launch), integer group dot products, plan fold 0.
 static int forward_q6k(const Act& x, const DeviceWeight& w, const Out& o, const Epi& e, hipStream_t st) {
   if (o.h16 || e.kind == kEpiGeluMul) {
     set_err("Q6_K: fp16 GEMM output and the fused dual epilogues are not available (the FFN entries run two passes)");
@@ -728,6 +730,17 @@ static int forward_q6k(const Act& x, const DeviceWeight& w, const Out& o, const 
   a.scale_t = w.scale_t;
   a.vec_ok = vec_aligned(x) ? 1 : 0;
   a.w = view(w, o.p, o.ld, e);
+  if (q8k_compute(w)) {
+    Q6kI8Geom g{};
+    if (!q6k_i8_geometry(x.m, x.k, w.ns, device_cus(), &g)) {
+      set_err("Q6_K in Q8_K arithmetic: K = %d is too long for the kernel's LDS staging of one activation row", x.k);
+      return -1;
+    }
+    return launch(planned(NAD_KERNEL_Q6K_I8, g.grid * g.passes, g.waves * 64, 1, 0), "Q6_K Q8_K-arithmetic kernel",
+                  [&] { return launch_q6k_i8(a, x.t, g, st); })
+               ? 0
+               : -1;
+  }
   if (x.m <= kSkinnyMaxM) {
     Q6kGemvGeom g{};
     if (!q6k_gemv_geometry(x.m, x.k, w.ns, x.t, device_cus(), &g)) {

@@ -84,13 +84,15 @@ constexpr uint64_t kGgufQ4_1 = 0x3154344655474700ull;  // "\0GGUF4Q1"
 constexpr uint64_t kGgufQ5_0 = 0x3054354655474700ull;  // "\0GGUF5Q0"
 constexpr uint64_t kGgufQ5_1 = 0x3154354655474700ull;  // "\0GGUF5Q1"
 constexpr uint64_t kGgufQ8_0 = 0x3054384655474700ull;  // "\0GGUF8Q0"
-// GGUF Q6_K (nad_q6_k_device_load): bits = 6, a layout and forward kernels of its own (woq_q6k.hip); fp arithmetic only
+// GGUF Q6_K (nad_q6_k_device_load): bits = 6, a layout and forward kernels of its own (woq_q6k.hip); fp arithmetic, or the
+// reference's Q8_K integer arithmetic as the weight's own mode 2
 constexpr uint64_t kGgufQ6_K = 0x4b51364655474700ull;  // "\0GGUF6QK"
 inline bool is_q6k(const nad::DeviceWeight& w) { return w.bits == 6; }
 // the activation quantizer of the weight's int8 arithmetic (its vec_dot_type, ne_layers.c:266-318): 0 the kblock
 // core's u8, 1 Q8_0 (Q4_0, Q5_0, Q8_0), 2 Q8_1 (Q4_1, Q5_1)
 int gguf_act_quant(const nad::DeviceWeight& w);
 bool int8_compute(const nad::DeviceWeight& w);  // a forward of this weight takes the int8 arithmetic right now
+bool q8k_compute(const nad::DeviceWeight& w);   // a Q6_K weight set to NAD_COMPUTE_Q8_K: forward_q6k takes woq_q6k_i8_kernel
 
 // ------------------------------------------------------------------------------------------------ load (capi_load.hip)
 // base: the host blob, scanned for codes the device cannot hold (load time only; null skips the scan)

@@ -480,6 +480,24 @@ extern "C" int nad_quant_q8_1(const void* act, int act_dtype, int m, int k, int 
   return 0;
 }
 
+extern "C" int nad_quant_q8_k(const void* act, int act_dtype, int m, int k, int lda, void* blocks, void* queue) {
+  if (!act || !blocks || m <= 0 || k <= 0 || k % 256 || lda < k) {  // before anything on the device is touched
+    set_err("nad_quant_q8_k: Q8_K needs non-null pointers, m > 0, k a positive multiple of 256 and lda >= k "
+            "(m=%d k=%d lda=%d)", m, k, lda);
+    return -1;
+  }
+  if (act_dtype != kActF32 && act_dtype != kActF16 && act_dtype != kActBF16) {
+    set_err("nad_quant_q8_k: Q8_K activations must be fp32, fp16 or bf16 (act_dtype=%d)", act_dtype);
+    return -1;
+  }
+  hipError_t e = launch_q8_k_quant(act, act_dtype, lda, m, k, blocks, static_cast<hipStream_t>(queue));
+  if (e != hipSuccess) {
+    set_err("Q8_K quantization launch failed: %s", hipGetErrorString(e));
+    return -1;
+  }
+  return 0;
+}
+
 // ------------------------------------------------------------------------------------------------ synthetic weights
 __global__ void nad_fill_u32_kernel(uint32_t* p, uint64_t n, uint64_t seed) {
   for (uint64_t i = blockIdx.x * uint64_t(blockDim.x) + threadIdx.x; i < n; i += uint64_t(gridDim.x) * blockDim.x) {

@@ -272,6 +272,18 @@ bool q6k_gemv_geometry(int m, int k, int ns, int act_t, int cus, Q6kGemvGeom* g)
 // a: A / lda / M / K, the epilogue operands and a.w (tiles = quants, zps = sub-scales, scales = d, nt = superblocks)
 hipError_t launch_q6k_gemv(const GemmArgs& a, int act_t, const Q6kGemvGeom& g, hipStream_t stream);
 hipError_t launch_q6k_gemm(const GemmArgs& a, int act_t, hipStream_t stream);  // grid: ceil(M / 128) * ceil(ns / 8)
+// quantize_row_q8_K_reference: act [m][lda] -> m rows of k/256 block_q8_K (292 bytes); k % 256 == 0
+hipError_t launch_q8_k_quant(const void* A, int act_t, int lda, int m, int k, void* blocks, hipStream_t stream);
+// Geometry of a woq_q6k_i8_kernel launch (the Q8_K integer arithmetic, any m): rows per pass (at most 16, fewer where
+// their codes and block sums do not fit LDS), the row sets of four a pass works on (1, 2 or 4), passes (grid.y) and LDS
+// bytes; false
+// when not even one row fits
+struct Q6kI8Geom {
+  int rows_pp, rs_pp, passes, grid, waves;
+  size_t lds;
+};
+bool q6k_i8_geometry(int m, int k, int ns, int cus, Q6kI8Geom* g);
+hipError_t launch_q6k_i8(const GemmArgs& a, int act_t, const Q6kI8Geom& g, hipStream_t stream);
 hipError_t launch_quant_u8(const QuantU8Args& a, int act_t, hipStream_t stream);
 hipError_t launch_i8(const I8Args& a, int bits, hipStream_t stream);
 hipError_t launch_gemm4(const GemmArgs& a, int bits, const _Float16* A16, int lda16, hipStream_t stream);

@@ -37,7 +37,9 @@
 //   zps    : the sub-scales, int8 [ns][k/256][16 n][16 groups]: lane l reads the 16 of its column with one 16-B load
 //   scales : d, fp16 [ns][k/256][16 n]
 // Padding columns of the last stripe hold v = 32 (q = 0), sc = 0 and d = 0.  asym stays 0: zps is no zero point here,
-// and no kernel but woq_q6k.hip's reads a bits = 6 weight.
+// and no kernel but woq_q6k.hip's reads a bits = 6 weight.  woq_q6k_i8_kernel (the weight's Q8_K integer mode) reads the
+// same layout: the nibble / crumb dwords of a group become its four bytes v = q + 32 with two shifts and two v_and_or
+// each, in element order 0, 2, 1, 3.
 #pragma once
 #include <cstdint>
 
@@ -75,8 +77,8 @@ struct DeviceWeight {
   int32_t blob_bs;    // the blob's own block size (per-channel: may exceed K; the int8-compute quantizer uses it)
   int32_t f4kind;     // NFloat weight: 0 F4_BNB, 1 F4_E2M1, 2 F4_NF4 (codes in the int4 layout, LUT dequant),
                       // 3 F8_E4M3, 4 F8_E5M2 (raw codes in the int8 layout); -1 = integer
-  int32_t compute;    // per-weight arithmetic (nad_device_set_compute): 0 follow the thread / process mode, 1 fp,
-                      // 2 int8 (integer-core blobs and the GGUF block types only)
+  int32_t compute;    // per-weight arithmetic (nad_device_set_compute, mode + 1): 0 follow the thread / process mode,
+                      // 1 fp, 2 int8 (integer-core blobs and the GGUF block types only), 3 Q8_K (GGUF Q6_K only)
   int32_t fold_ok;    // every (q - zp) * scale of the weight is 0 or an fp16 normal: the prefill GEMMs may fold the
                       // group scale into the fp16 B fragment (checked at load)
   void* mins;         // fp16 block mins of GGUF Q4_1 / Q5_1 (nullptr: the weight has none); the GGUF type itself is

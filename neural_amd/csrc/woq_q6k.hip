@@ -1,6 +1,7 @@
 // woq_q6k.hip -- GGUF Q6_K weights (neural_speed/core/data_types.h:133-138; dequantize_row_q6_K,
 // vectors/cpu/quantize.h:956-999) at the file's own 6.5625 bits per weight: the repack into the layout of woq_layout.h,
-// the unpack check, and the two forward kernels.
+// the unpack check, the two fp forward kernels, and -- the weight's own mode NAD_COMPUTE_Q8_K -- the reference's Q8_K
+// activation quantizer and integer forward (woq_q6k_i8_kernel, below).
 //
 // A superblock is 256 weights w = d * sc * q: q in -32..31 (low nibbles in ql, high crumbs in qh), an int8 sc per 16
 // weights, one fp16 d.  The quantizer writes sc up to +-127, so |sc * q| reaches 4096 and an fp16 B fragment holding
@@ -24,6 +25,7 @@ namespace nad {
 typedef _Float16 h4_t __attribute__((ext_vector_type(4)));
 
 constexpr int kQ6kBlockBytes = 210;  // ql[128] qh[64] scales[16] d
+constexpr int kQ8kBlockBytes = 292;  // block_q8_K: float d, int8 qs[256], int16 bsums[16]
 constexpr int kQ6kWaves = 16;        // waves of a GEMV workgroup = K-slices of a stripe
 constexpr size_t kQ6kLdsMax = 160 * 1024;
 constexpr size_t kQ6kPartBytes = 2 * kQ6kWaves * 1024;  // two sets of per-wave 16 x 16 fp32 partials
@@ -313,8 +315,8 @@ bool q6k_gemv_geometry(int m, int k, int ns, int act_t, int cus, Q6kGemvGeom* g)
   return true;
 }
 
-template <auto K>
-static hipError_t q6k_launch_lds(dim3 g, dim3 b, size_t lds, hipStream_t st, const Q6kGemvArgs& args) {
+template <auto K, class Args>
+static hipError_t q6k_launch_lds(dim3 g, dim3 b, size_t lds, hipStream_t st, const Args& args) {
   static bool attr_set = false;  // opt the kernel in to > 64 KiB of dynamic LDS once
   if (!attr_set) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -485,6 +487,408 @@ hipError_t launch_q6k_gemm(const GemmArgs& a, int act_t, hipStream_t st) {
   else
     hipLaunchKernelGGL(woq_q6k_gemm_kernel<kActBF16>, grid, dim3(512), 0, st, a);
   return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------ Q8_K activations
+// quantize_row_q8_K_reference (vectors/cpu/quantize.h:1020-1055) for one superblock of one row, by one wave: lane l
+// holds x[4 l .. 4 l + 3].  max is the signed value of the first element with the strictly largest |x|: the lane's own
+// first one, then the one of the lowest lane whose largest |x| equals the wave's (lane order is element order).  The
+// wave's largest |x| is reduced on the bit patterns (non-negative floats order as unsigned integers) with DPP inside
+// the rows of 16 lanes and four v_readlane across them: no LDS round trip;
+// iscale = -128 / max, q = min(127, nearest_int(iscale * x))
+// with the reference's magic-number rounding and no contraction of the product into the add, d = 1 / iscale.  Returns
+// the lane's four codes (byte j = element 4 l + j), d, and the sum of the 16 codes of group l >> 2.  An all-zero
+// superblock gives d = 0, codes 0 and sums 0.  Every lane of the wave must call it.
+template <int CTRL>
+__device__ __forceinline__ int q8k_dpp(int v) {  // v of the lane the DPP control selects (all lanes active)
+  return __builtin_amdgcn_update_dpp(v, v, CTRL, 0xf, 0xf, true);
+}
+constexpr int kDppXor1 = 0xB1, kDppXor2 = 0x4E;              // quad_perm [1,0,3,2] / [2,3,0,1]
+constexpr int kDppHalfMirror = 0x141, kDppRowMirror = 0x140;  // lane i <-> 7 - i of its 8 / 15 - i of its 16
+struct Q8kLane {
+  uint32_t codes;
+  float d;
+  int bsum;
+};
+__device__ __forceinline__ Q8kLane q8k_quant_wave(const float (&x)[4], int lane) {
+#pragma clang fp contract(off)
+  float lmax = 0.f, lmx = 0.f;
+#pragma unroll
+  for (int j = 0; j < 4; j++) {
+    const float ax = fabsf(x[j]);
+    if (ax > lmax) {
+      lmax = ax;
+      lmx = x[j];
+    }
+  }
+  const uint32_t lbits = __float_as_uint(lmax);
+  uint32_t rmax = lbits;
+  rmax = max(rmax, uint32_t(q8k_dpp<kDppXor1>(int(rmax))));
+  rmax = max(rmax, uint32_t(q8k_dpp<kDppXor2>(int(rmax))));
+  rmax = max(rmax, uint32_t(q8k_dpp<kDppHalfMirror>(int(rmax))));
+  rmax = max(rmax, uint32_t(q8k_dpp<kDppRowMirror>(int(rmax))));
+  const uint32_t amax = max(max(uint32_t(__builtin_amdgcn_readlane(int(rmax), 0)),
+                                uint32_t(__builtin_amdgcn_readlane(int(rmax), 16))),
+                            max(uint32_t(__builtin_amdgcn_readlane(int(rmax), 32)),
+                                uint32_t(__builtin_amdgcn_readlane(int(rmax), 48))));
+  Q8kLane r{0u, 0.f, 0};
+  const int first = __builtin_ctzll(__ballot(lbits == amax));  // wave-uniform; some lane holds amax, so the mask is not 0
+  const float mx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(lmx), first));
+  // an all-zero superblock takes iscale = 0 (every code 0) and d = 0 with no branch, so that the quantizations a wave
+  // runs side by side interleave
+  const float iscale = mx != 0.f ? -128.f / mx : 0.f;
+  int s = 0;
+#pragma unroll
+  for (int j = 0; j < 4; j++) {
+    const float p = iscale * x[j];
+    const float val = p + 12582912.f;
+    int q = (__float_as_int(val) & 0x007fffff) - 0x00400000;
+    q = min(127, q);
+    s += q;
+    r.codes |= uint32_t(q & 0xff) << (8 * j);
+  }
+  s += q8k_dpp<kDppXor1>(s);
+  s += q8k_dpp<kDppXor2>(s);
+  r.bsum = s;
+  r.d = mx != 0.f ? 1.f / iscale : 0.f;
+  return r;
+}
+
+// The four activations A[row][k0 .. k0 + 3]: the loads (load_a4_raw: one 16- or 8-byte load where the rows are 16-byte
+// aligned, VEC, else four element loads) apart from the conversion to fp32 (cvt_a4), so that a wave can send the loads
+// of several superblocks before it waits for the first
+template <int AT, bool VEC>
+__device__ __forceinline__ u4_t load_a4_raw(const void* A, int lda, int row, int k0) {
+  const size_t base = size_t(row) * lda + k0;
+  if constexpr (AT == kActF32) {
+    const uint32_t* p = static_cast<const uint32_t*>(A) + base;
+    if constexpr (VEC) return *reinterpret_cast<const u4_t*>(p);
+    return u4_t{p[0], p[1], p[2], p[3]};
+  } else {
+    const uint16_t* p = static_cast<const uint16_t*>(A) + base;
+    if constexpr (VEC) {
+      const uint2 x = *reinterpret_cast<const uint2*>(p);
+      return u4_t{x.x, x.y, 0u, 0u};
+    }
+    return u4_t{p[0], p[1], p[2], p[3]};
+  }
+}
+template <int AT, bool VEC>
+__device__ __forceinline__ void cvt_a4(const u4_t& raw, float (&v)[4]) {
+#pragma unroll
+  for (int j = 0; j < 4; j++) {
+    if constexpr (AT == kActF32) {
+      v[j] = __uint_as_float(raw[j]);
+    } else {
+      const uint16_t h = VEC ? uint16_t(raw[j >> 1] >> (16 * (j & 1))) : uint16_t(raw[j]);
+      v[j] = AT == kActF16 ? f16_bits_to_f32(h) : bf16_bits_to_f32(h);
+    }
+  }
+}
+
+// block_q8_K rows {float d; int8 qs[256]; int16 bsums[16]}: one wave per (row, superblock)
+struct Q8kArgs {
+  const void* A;
+  int lda, M, K, vec_ok;
+  char* blocks;
+};
+template <int AT>
+__global__ __launch_bounds__(256) void nad_q8_k_quant_kernel(Q8kArgs a) {
+  const int nsb = a.K / 256;
+  const int lane = threadIdx.x & 63;
+  const int64_t idx = int64_t(blockIdx.x) * 4 + (threadIdx.x >> 6);  // wave-uniform
+  if (idx >= int64_t(a.M) * nsb) return;
+  const int row = int(idx / nsb), b = int(idx % nsb);
+  float x[4];
+  if (a.vec_ok)
+    cvt_a4<AT, true>(load_a4_raw<AT, true>(a.A, a.lda, row, 256 * b + 4 * lane), x);
+  else
+    cvt_a4<AT, false>(load_a4_raw<AT, false>(a.A, a.lda, row, 256 * b + 4 * lane), x);
+  const Q8kLane q = q8k_quant_wave(x, lane);
+  char* blk = a.blocks + size_t(idx) * kQ8kBlockBytes;  // 292 = 4 * 73: every field keeps its alignment
+  if (lane == 0) *reinterpret_cast<float*>(blk) = q.d;
+  *reinterpret_cast<uint32_t*>(blk + 4 + 4 * lane) = q.codes;
+  if ((lane & 3) == 0) *reinterpret_cast<int16_t*>(blk + 260 + 2 * (lane >> 2)) = int16_t(q.bsum);
+}
+
+hipError_t launch_q8_k_quant(const void* A, int act_t, int lda, int m, int k, void* blocks, hipStream_t st) {
+  if (m < 1 || k < 256 || k % 256 != 0 || !A || !blocks) return hipErrorInvalidValue;
+  const int esz = act_t == kActF32 ? 4 : 2;
+  const bool vec_ok = reinterpret_cast<uintptr_t>(A) % 16 == 0 && (size_t(lda) * esz) % 16 == 0;
+  const Q8kArgs a{A, lda, m, k, vec_ok ? 1 : 0, static_cast<char*>(blocks)};
+  const int64_t total = int64_t(m) * (k / 256);
+  const dim3 grid(unsigned((total + 3) / 4)), block(256);
+  if (act_t == kActF32)
+    hipLaunchKernelGGL(nad_q8_k_quant_kernel<kActF32>, grid, block, 0, st, a);
+  else if (act_t == kActF16)
+    hipLaunchKernelGGL(nad_q8_k_quant_kernel<kActF16>, grid, block, 0, st, a);
+  else
+    hipLaunchKernelGGL(nad_q8_k_quant_kernel<kActBF16>, grid, block, 0, st, a);
+  return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------ Q8_K integer forward
+// ggml_vec_dot_q6_K_q8_K's arithmetic (core/layers/vec_dot.h:1190-1231) on v_mfma_i32_16x16x64_i8.  Per output row r,
+// column c and superblock b:
+//   isum_b = sum_{g < 16} sc[g] * sum_{i < 16} q[16 g + i] * a[16 g + i]        exact in int32 (|isum_b| <= 2^27)
+//   y      = sum_b fp32(fp32(d_w[b]) * d_a[r][b]) * float(isum_b)              fp32
+// in this order: a wave adds its superblocks b = wave, wave + 16, ... in ascending order with one fma each onto 0, and
+// one wave adds the 16 waves' partials in wave order (the reference's eight interleaved fp32 partials are not
+// reproduced).
+//
+// The workgroup structure is woq_q6k_gemv_kernel's.  Staging quantizes the pass's rows with q8k_quant_wave, a wave per
+// (row, superblock), and leaves in LDS: the codes (row stride K + 64 bytes: the four rows a fragment read touches fall
+// in different banks; inside every run of four k the bytes are in the order 0, 2, 1, 3, the order the weight bytes
+// come out of the nibble / crumb dwords with the fewest operations), d_a as [superblock][16 rows], and -32 times the
+// block sums as int32 [superblock][row set][4 rows][group].
+//
+// One MFMA issue spans four groups (64 k).  The lane's B operand is the four dwords of stored values v = q + 32
+// (0 .. 63) of groups 4 t .. 4 t + 3: B[k slot (kq, i, j)][n = nl] = v[16 (4 t + i) + 4 kq + j].  A row 4 m + i holds
+// the codes of activation row m (of the row set) in dword i alone, zeros elsewhere, so C row 4 m + i is the dot
+// product of group 4 t + i for row m -- and by the C/D map (row = 4 (lane >> 4) + reg) lane (nl, kq) holds in register
+// i the dot product of group 4 t + i for row kq, whose sub-scale is byte i of dword t of the 16 the lane already has.
+// The C input is -32 * bsum of that (row, group): sum (v - 32) a = sum v a - 32 bsum, exact.  isum += sc * C is one
+// v_mad_i32_i24 per group (|C| <= 2^16), so after the four issues of a superblock the lane holds the whole isum of
+// its (row, column) with no exchange between lanes.  Four issues per superblock and row set of four rows.
+typedef int i4_t __attribute__((ext_vector_type(4)));
+
+struct Q6kI8Args {
+  GemmArgs g;
+  int rows_pp, rs_pp;  // activation rows per pass; row sets of four the pass works on (the kernel's RS)
+};
+
+// the bytes v of group G (elements 4 kq + 0, 2, 1, 3 in bytes 0 .. 3) from the lane's nibble and crumb dwords
+template <int S>
+__device__ __forceinline__ uint32_t q6k_shl(uint32_t x) {  // x << S, S < 0: x >> -S
+  if constexpr (S >= 0) return x << S;
+  return x >> (-S);
+}
+template <int G>
+__device__ __forceinline__ uint32_t q6k_bytes(const u4_t& lo0, const u4_t& lo1, const u4_t& hi) {
+  const uint32_t lo = (G < 8 ? lo0 : lo1)[(G & 7) >> 1];
+  const uint32_t hw = hi[G >> 2];
+  constexpr int GP = G & 1, G4 = G & 3;
+  const uint32_t x = GP ? lo >> 8 : lo;
+  uint32_t t = x & 0x000F000Fu;
+  t = dq_and_or(x << 4, 0x0F000F00u, t);
+  t = dq_and_or(q6k_shl<4 - 4 * G4>(hw), 0x00300030u, t);
+  return dq_and_or(q6k_shl<10 - 4 * G4>(hw), 0x30003000u, t);
+}
+
+// RS: the row sets of four rows a pass works on (1: the decode case; 2; 4) = Q6kI8Geom::rs_pp.  All RS of them are
+// staged and multiplied with no test on the row count, so that the LDS reads and the MFMAs of the row sets of one
+// issue go out together; rows past mloc are zeros (d_a = 0) and are not written out.
+template <int AT, int RS>
+__global__ __launch_bounds__(kQ6kWaves * 64) void woq_q6k_i8_kernel(Q6kI8Args qa) {
+  extern __shared__ __attribute__((aligned(16))) char q6k_lds[];
+  const GemmArgs& a = qa.g;
+  const SkinnyWeight& W = a.w;
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave-uniform: scalar
+  const int nl = lane & 15, kq = lane >> 4;
+  const int nsb = W.nt, ns = W.ns, K = a.K;
+  const int row0 = blockIdx.y * qa.rows_pp;
+  const int mloc = min(qa.rows_pp, a.M - row0);
+  constexpr int rs_pp = RS;
+  const int rstride = K + 64;
+  char* codes = q6k_lds;
+  float* da = reinterpret_cast<float*>(q6k_lds + size_t(qa.rows_pp) * rstride);
+  int* nb = reinterpret_cast<int*>(da + size_t(nsb) * 16);
+  float* part = reinterpret_cast<float*>(nb + size_t(nsb) * rs_pp * 64);
+
+  const u4_t* qp = static_cast<const u4_t*>(W.tiles);
+  const u4_t* scp = reinterpret_cast<const u4_t*>(W.zps);
+  const u4_t* dp = static_cast<const u4_t*>(W.scales);
+  const bool has = wave < nsb;
+  u4_t c0{}, c1{}, c2{}, csc{}, cd{};
+  auto fetch = [&](int s, int b, u4_t& l0, u4_t& l1, u4_t& h, u4_t& sc, u4_t& d) {
+    const size_t sb = size_t(s) * nsb + b;
+    const u4_t* t = qp + sb * 192 + lane;
+    l0 = __builtin_nontemporal_load(t);
+    l1 = __builtin_nontemporal_load(t + 64);
+    h = __builtin_nontemporal_load(t + 128);
+    sc = __builtin_nontemporal_load(scp + sb * 16 + nl);
+    d = __builtin_nontemporal_load(dp + sb * 2 + (nl >> 3));
+  };
+  int s = blockIdx.x;
+  if (has && s < ns) fetch(s, wave, c0, c1, c2, csc, cd);
+
+  // stage: a wave per (row, superblock) over the 4 RS rows of the pass's row sets, U at a time with their loads sent
+  // together.  Rows past mloc get d_a = 0 and zero sums (their codes are never read: the fragment reads below take
+  // row 0 instead)
+  auto stage = [&](auto vec) {
+    constexpr bool VEC = decltype(vec)::value;
+    constexpr int U = RS == 1 ? 4 : 8;
+    constexpr int rows = 4 * RS;
+    // the wave's tasks are wave, wave + 16, ... of the rows * nsb in (row, superblock) order; (tr, tb) is its next one
+    const int q16 = kQ6kWaves / nsb, r16 = kQ6kWaves - q16 * nsb;
+    int tr = wave / nsb, tb = wave - tr * nsb;
+    u4_t raw[U];
+    int rr[U], bb[U];
+    // no branch in here (the loads stay back to back, and the first batch goes out right behind the weight loads
+    // above): a task of a row past mloc loads what the last real row's does and the value is dropped below
+    auto load = [&]() {
+#pragma unroll
+      for (int u = 0; u < U; u++) {
+        rr[u] = tr;
+        bb[u] = tb;
+        raw[u] = load_a4_raw<AT, VEC>(a.A, a.lda, row0 + min(tr, mloc - 1), 256 * tb + 4 * lane);
+        tr += q16;
+        tb += r16;
+        if (tb >= nsb) {
+          tb -= nsb;
+          tr++;
+        }
+      }
+    };
+    load();
+    while (rr[0] < rows) {
+#pragma unroll
+      for (int u = 0; u < U; u++) {
+        const int r = rr[u], b = bb[u];
+        if (r < rows) {
+          Q8kLane q{0u, 0.f, 0};
+          if (r < mloc) {
+            float x[4];
+            cvt_a4<AT, VEC>(raw[u], x);
+            q = q8k_quant_wave(x, lane);
+            *reinterpret_cast<uint32_t*>(codes + size_t(r) * rstride + 256 * b + 4 * lane) =
+                __builtin_amdgcn_perm(0u, q.codes, 0x03010200u);
+          }
+          if (lane == 0) da[b * 16 + r] = q.d;
+          if ((lane & 3) == 0) nb[((b * rs_pp + (r >> 2)) * 4 + (r & 3)) * 16 + (lane >> 2)] = -32 * q.bsum;
+        }
+      }
+      if (tr >= rows) break;
+      load();
+    }
+  };
+  if (a.vec_ok)
+    stage(std::true_type{});
+  else
+    stage(std::false_type{});
+  __syncthreads();
+
+  // A row nl = 4 m + i: dword i of the fragment, activation row m of the row set
+  const int ai = nl & 3, am = nl >> 2;
+  const uint32_t am0 = ai == 0 ? ~0u : 0u, am1 = ai == 1 ? ~0u : 0u, am2 = ai == 2 ? ~0u : 0u, am3 = ai == 3 ? ~0u : 0u;
+  const char* abase[RS];
+#pragma unroll
+  for (int rs = 0; rs < RS; rs++) {
+    const int r = 4 * rs + am;
+    abase[rs] = codes + size_t(r < mloc ? r : 0) * rstride + 16 * ai + 4 * kq;
+  }
+  for (int it = 0; s < ns; s += gridDim.x, it++) {
+    float acc[RS];  // row 4 rs + kq, column nl
+#pragma unroll
+    for (int rs = 0; rs < RS; rs++) acc[rs] = 0.f;
+    if (has) {
+      for (int b = wave; b < nsb; b += kQ6kWaves) {
+        int s2 = s, b2 = b + kQ6kWaves;
+        if (b2 >= nsb) {
+          s2 = s + gridDim.x;
+          b2 = wave;
+        }
+        u4_t n0 = c0, n1 = c1, n2 = c2, nsc = csc, nd = cd;
+        if (s2 < ns) fetch(s2, b2, n0, n1, n2, nsc, nd);
+        int isum[RS];
+#pragma unroll
+        for (int rs = 0; rs < RS; rs++) isum[rs] = 0;
+        auto issue = [&](auto tc) {
+          constexpr int T = decltype(tc)::value;
+          const i4_t bf{int(q6k_bytes<4 * T>(c0, c1, c2)), int(q6k_bytes<4 * T + 1>(c0, c1, c2)),
+                        int(q6k_bytes<4 * T + 2>(c0, c1, c2)), int(q6k_bytes<4 * T + 3>(c0, c1, c2))};
+          const int scw = int(csc[T]);
+#pragma unroll
+          for (int rs = 0; rs < RS; rs++) {
+            {
+              const uint32_t av = *reinterpret_cast<const uint32_t*>(abase[rs] + 256 * b + 64 * T);
+              const i4_t af{int(av & am0), int(av & am1), int(av & am2), int(av & am3)};
+              const i4_t cin = *reinterpret_cast<const i4_t*>(nb + ((b * rs_pp + rs) * 4 + kq) * 16 + 4 * T);
+              const i4_t c = __builtin_amdgcn_mfma_i32_16x16x64_i8(af, bf, cin, 0, 0, 0);
+#pragma unroll
+              for (int i = 0; i < 4; i++) isum[rs] += __mul24(__builtin_amdgcn_sbfe(scw, 8 * i, 8), c[i]);
+            }
+          }
+        };
+        issue(std::integral_constant<int, 0>{});
+        issue(std::integral_constant<int, 1>{});
+        issue(std::integral_constant<int, 2>{});
+        issue(std::integral_constant<int, 3>{});
+        const float df = q6k_d(cd, nl);
+#pragma unroll
+        for (int rs = 0; rs < RS; rs++) {
+          {
+            const float f = df * da[b * 16 + 4 * rs + kq];
+            acc[rs] = __builtin_fmaf(f, float(isum[rs]), acc[rs]);
+          }
+        }
+        c0 = n0;
+        c1 = n1;
+        c2 = n2;
+        csc = nsc;
+        cd = nd;
+      }
+    }
+    // partial of this wave: rows 4 rs + kq, column nl (the rows of an RS = 1 launch are 0 .. 3: the reduce below
+    // writes out rows below mloc <= 4 only)
+    float* slot = part + size_t(it & 1) * (kQ6kWaves * 256);
+#pragma unroll
+    for (int rs = 0; rs < RS; rs++) slot[wave * 256 + (4 * rs + kq) * 16 + nl] = acc[rs];
+    __syncthreads();
+    if (wave == (it & (kQ6kWaves - 1))) {
+      const int row = lane >> 2, n0 = 4 * (lane & 3);
+      float v[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+      for (int w = 0; w < kQ6kWaves; w++) {  // wave order
+        const float4 pv = *reinterpret_cast<const float4*>(slot + w * 256 + row * 16 + n0);
+        v[0] += pv.x;
+        v[1] += pv.y;
+        v[2] += pv.z;
+        v[3] += pv.w;
+      }
+      if (row < mloc && s * 16 + n0 < W.n) gemm_epilogue4(a, row0 + row, s * 16 + n0, v);
+    }
+  }
+}
+
+bool q6k_i8_geometry(int m, int k, int ns, int cus, Q6kI8Geom* g) {
+  // per row: K + 64 code bytes; per row set: 256 bytes of sums per superblock; d_a: 64 bytes per superblock
+  const size_t nsb = size_t(k) / 256, budget = kQ6kLdsMax - kQ6kPartBytes;
+  auto need = [&](int rows) {
+    return size_t(rows) * (size_t(k) + 64) + nsb * 64 + nsb * size_t(rows <= 4 ? 1 : (rows <= 8 ? 2 : 4)) * 256;
+  };
+  int rows = std::min(m, 16);
+  while (rows >= 1 && need(rows) > budget) rows--;
+  if (rows < 1) return false;
+  g->rows_pp = rows;
+  g->rs_pp = rows <= 4 ? 1 : (rows <= 8 ? 2 : 4);
+  g->passes = (m + rows - 1) / rows;
+  g->grid = std::max(1, std::min(ns, cus));
+  g->waves = kQ6kWaves;
+  g->lds = need(rows) + kQ6kPartBytes;
+  return true;
+}
+
+hipError_t launch_q6k_i8(const GemmArgs& a, int act_t, const Q6kI8Geom& g, hipStream_t st) {
+  if (a.M < 1 || a.K < 256 || a.K % 256 != 0 || g.lds > kQ6kLdsMax || g.rows_pp < 1 || g.rows_pp > 16 ||
+      g.passes != (a.M + g.rows_pp - 1) / g.rows_pp || g.passes > 65535)
+    return hipErrorInvalidValue;
+  Q6kI8Args qa{a, g.rows_pp, g.rs_pp};
+  const dim3 grid(g.grid, g.passes), block(kQ6kWaves * 64);
+  if (g.rs_pp != (g.rows_pp <= 4 ? 1 : (g.rows_pp <= 8 ? 2 : 4))) return hipErrorInvalidValue;
+  if (g.rs_pp == 1) {
+    if (act_t == kActF32) return q6k_launch_lds<woq_q6k_i8_kernel<kActF32, 1>>(grid, block, g.lds, st, qa);
+    if (act_t == kActF16) return q6k_launch_lds<woq_q6k_i8_kernel<kActF16, 1>>(grid, block, g.lds, st, qa);
+    return q6k_launch_lds<woq_q6k_i8_kernel<kActBF16, 1>>(grid, block, g.lds, st, qa);
+  }
+  if (g.rs_pp == 2) {
+    if (act_t == kActF32) return q6k_launch_lds<woq_q6k_i8_kernel<kActF32, 2>>(grid, block, g.lds, st, qa);
+    if (act_t == kActF16) return q6k_launch_lds<woq_q6k_i8_kernel<kActF16, 2>>(grid, block, g.lds, st, qa);
+    return q6k_launch_lds<woq_q6k_i8_kernel<kActBF16, 2>>(grid, block, g.lds, st, qa);
+  }
+  if (act_t == kActF32) return q6k_launch_lds<woq_q6k_i8_kernel<kActF32, 4>>(grid, block, g.lds, st, qa);
+  if (act_t == kActF16) return q6k_launch_lds<woq_q6k_i8_kernel<kActF16, 4>>(grid, block, g.lds, st, qa);
+  return q6k_launch_lds<woq_q6k_i8_kernel<kActBF16, 4>>(grid, block, g.lds, st, qa);
 }
 
 }  // namespace nad

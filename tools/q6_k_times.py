@@ -1,5 +1,6 @@
-"""Device time of one GGUF Q6_K forward next to Q8_0 (the int8 g32 path: what a Q6_K tensor had to be requantized to
-before this layout existed), same shapes, same run, alternating (development tool).  Cold weights: the forwards of a
+"""Device time of one GGUF Q6_K forward -- in fp (the default) and in the weight's COMPUTE_Q8_K mode (woq_q6k_i8_kernel:
+Q8_K activation rows, integer dot products) -- next to Q8_0 (the int8 g32 path: what a Q6_K tensor had to be
+requantized to before this layout existed), same shapes, same run, alternating (development tool).  Cold weights: the forwards of a
 captured graph rotate over copies of the weight that together exceed the 256 MB Infinity Cache; HIP graph replay, HIP
 events on the launch stream (the method of tools/gguf_types_times.py).  Each figure is the median of --rounds
 alternating rounds, with the spread (min .. max) beside it.  For M = 1 the achieved bandwidth is the algorithmic bytes
@@ -50,14 +51,17 @@ def main():
     esz = 4 if args.act == "fp32" else 2
     print(f"{torch.cuda.get_device_name()}  act {args.act}; us per forward (median of {args.rounds} alternating rounds, "
           f"min .. max), cold weights")
-    print(f"{'N x K':<14}{'M':>6}  {'Q6_K us':>26}  {'Q8_0 us':>26}  {'Q6_K/Q8_0':>9}  {'Q6_K TB/s':>9}  {'Q8_0 TB/s':>9}  kernels")
+    print(f"{'N x K':<14}{'M':>6}  {'Q6_K us':>26}  {'Q6_K in Q8_K mode us':>26}  {'Q8_0 us':>26}  {'Q6_K/Q8_0':>9}  "
+          f"{'mode/fp':>7}  {'Q6_K TB/s':>9}  {'mode TB/s':>9}  {'Q8_0 TB/s':>9}  kernels")
     for spec in args.shapes.split(";"):
         shape, ms = spec.split(":")
         n, k = (int(v) for v in shape.split("x"))
-        wbytes = {"q6": n * k // 256 * 210, "q8": n * k // 32 * 34}
+        wbytes = {"q6": n * k // 256 * 210, "q6i": n * k // 256 * 210, "q8": n * k // 32 * 34}
         b6, b8 = q6_k_blocks(np, n, k, 6), q8_0_blocks(np, n, k, 8)
         ws = {"q6": [bestla.DeviceWeight.from_q6_k(b6, n, k)
                      for _ in range(max(2, math.ceil(args.mb * 1e6 / wbytes["q6"])))],
+              "q6i": [bestla.DeviceWeight.from_q6_k(b6, n, k).set_compute(bestla.COMPUTE_Q8_K)
+                      for _ in range(max(2, math.ceil(args.mb * 1e6 / wbytes["q6i"])))],
               "q8": [bestla.DeviceWeight.from_gguf(bestla.GGUF_Q8_0, b8, n, k)
                      for _ in range(max(2, math.ceil(args.mb * 1e6 / wbytes["q8"])))]}
         for m in (int(v) for v in ms.split(",")):
@@ -66,7 +70,7 @@ def main():
             reps = args.reps if m <= 256 else max(4, args.reps // 4)
             s = torch.cuda.Stream()
             s.wait_stream(torch.cuda.current_stream())
-            graphs, times = {}, {"q6": [], "q8": []}
+            graphs, times = {}, {"q6": [], "q6i": [], "q8": []}
             with torch.cuda.stream(s):
                 for key, wl in ws.items():
                     for i in range(max(len(wl), 2)):  # warm up every weight copy and the shape
@@ -78,7 +82,7 @@ def main():
                     g.replay()
                     graphs[key] = g
                 for _ in range(args.rounds):
-                    for key in ("q6", "q8"):
+                    for key in ("q6", "q6i", "q8"):
                         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                         e0.record(s)
                         for _ in range(args.replays):
@@ -90,10 +94,11 @@ def main():
             med = {key: statistics.median(v) for key, v in times.items()}
             cell = {key: f"{med[key]:9.2f} ({min(v):.2f} .. {max(v):.2f})" for key, v in times.items()}
             tbs = {key: (wbytes[key] + k * esz + n * 4) / (med[key] * 1e-6) / 1e12 for key in med}
-            bw = f"{tbs['q6']:9.2f}  {tbs['q8']:9.2f}" if m == 1 else f"{'':>9}  {'':>9}"
-            kern = ws["q6"][0].plan(m, args.act)["kernel"] + " / " + ws["q8"][0].plan(m, args.act)["kernel"]
-            print(f"{shape:<14}{m:>6}  {cell['q6']:>26}  {cell['q8']:>26}  {med['q6'] / med['q8']:9.2f}  {bw}  {kern}",
-                  flush=True)
+            bw = (f"{tbs['q6']:9.2f}  {tbs['q6i']:9.2f}  {tbs['q8']:9.2f}" if m == 1
+                  else f"{'':>9}  {'':>9}  {'':>9}")
+            kern = " / ".join(ws[key][0].plan(m, args.act)["kernel"] for key in ("q6", "q6i", "q8"))
+            print(f"{shape:<14}{m:>6}  {cell['q6']:>26}  {cell['q6i']:>26}  {cell['q8']:>26}  "
+                  f"{med['q6'] / med['q8']:9.2f}  {med['q6i'] / med['q6']:7.2f}  {bw}  {kern}", flush=True)
             del graphs
         del ws
         torch.cuda.empty_cache()
