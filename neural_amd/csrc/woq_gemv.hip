@@ -328,16 +328,31 @@ __device__ __forceinline__ float reduce_slots(const float* ps, int nwl) {
   return (s0 + s1) + (s2 + s3);
 }
 
-// The M = 1 kernels lay their slots out per column, [nv][16 columns][NW], so that a launch of 16 waves with a K-slice
-// each reduces with four 16-B LDS reads per output and no per-slot clamps: the same order as reduce_slots at 16, whose
-// 16 clamped offsets + masks are ~100 scalar instructions executed once per launch, cold in the instruction cache
-// (~0.4 us per KB).  Measured (profiles/r06_gemv_tail_ab.txt, same box, alternating): O 4.80 -> 4.55 us, decode
-// 946-951 -> 969-972 tok/s; bit-identical sums.
-__device__ __forceinline__ float reduce16(const float* col) {
+// The M = 1 kernels lay their slots out per column, [nv][16 columns][slot stride], so that a launch whose slot count N
+// is known at compile time (the stride is then N rounded up to 4) reduces with N / 4 rounded up 16-B LDS reads per
+// output and no per-slot clamps: the same order as reduce_slots at N, whose 16 clamped offsets + masks are ~100 scalar
+// instructions executed once per launch, cold in the instruction cache (~0.4 us per KB).  Measured at N = 16
+// (profiles/r06_gemv_tail_ab.txt, same box, alternating): O 4.80 -> 4.55 us, decode 946-951 -> 969-972 tok/s;
+// bit-identical sums.
+template <int N>
+__device__ __forceinline__ float reduce_fixed(const float* col) {
+  static_assert(N >= 4 && N <= 16, "at least one whole group of four");
+  constexpr int NV = (N + 3) / 4, FULL = N / 4;
   const float4* ps = reinterpret_cast<const float4*>(col);
-  const float4 t0 = ps[0], t1 = ps[1], t2 = ps[2], t3 = ps[3];
-  const float s0 = ((t0.x + t1.x) + t2.x) + t3.x, s1 = ((t0.y + t1.y) + t2.y) + t3.y;
-  const float s2 = ((t0.z + t1.z) + t2.z) + t3.z, s3 = ((t0.w + t1.w) + t2.w) + t3.w;
+  float4 t[NV];
+#pragma unroll
+  for (int i = 0; i < NV; i++) t[i] = ps[i];
+  float s0 = t[0].x, s1 = t[0].y, s2 = t[0].z, s3 = t[0].w;
+#pragma unroll
+  for (int i = 1; i < FULL; i++) {
+    s0 += t[i].x;
+    s1 += t[i].y;
+    s2 += t[i].z;
+    s3 += t[i].w;
+  }
+  if constexpr (N % 4 > 0) s0 += t[FULL].x;
+  if constexpr (N % 4 > 1) s0 += t[FULL].y;
+  if constexpr (N % 4 > 2) s0 += t[FULL].z;
   return (s0 + s1) + (s2 + s3);
 }
 
@@ -677,7 +692,8 @@ static bool lean_ok(const GemvArgs& a, int bits, int waves) {
 //   P::act_rsrc, P::act_live      the activations' buffer resource and which of a wave's loads are in range
 //   P::cursor_start, P::load      the stage loader (two-armed load_stage / select-based m1s_load_stage: both were
 //                                 measured separately and both stay)
-// and the wave count NW as a value (blockDim, the argument block's, or the literal 16).
+// and the wave count NW and the slot stride PS of a column's partial sums as values (blockDim, the argument block's,
+// or literals).
 struct M1General {
   using Args = GemvArgs;
   static __device__ __forceinline__ __amdgpu_buffer_rsrc_t act_rsrc(const Args& a, int esz) { return rsrc(a.A, a.K * esz); }
@@ -699,7 +715,7 @@ struct M1General {
 
 template <class P, int BITS, int GPT, int AT, bool ASYM, int KSN, int SPW, int NST, int ST>
 __device__ __forceinline__ void m1_stream(const typename P::Args& a, int lane, int wave, int NW, int nsl, int v0,
-                                          int nv, bool idle, float* part) {
+                                          int nv, bool idle, float* part, int PS) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int KT = k_tile(BITS);
   constexpr int RB = lean_row_bytes(BITS, KSN);  // one fp16 row of a slice
@@ -769,10 +785,30 @@ __device__ __forceinline__ void m1_stream(const typename P::Args& a, int lane, i
   f4_t acc = {0.f, 0.f, 0.f, 0.f};
   int cj = idle ? nv : 0, cq = wave, cs = 0;  // compute cursor: local stripe, K-slice, slice ordinal of this wave
 
+#ifdef NAD_PHASE_TRACE
+  // slots 5-7: wave 0's arithmetic time of its first stage, of all later stages, and the stage count -- each stage
+  // timed from an explicit wait for its loads to its last MFMA result (is the stream body's code, first executed when
+  // nothing else is pending, fetched late?)
+  unsigned long long tr_first = 0, tr_later = 0, tr_k = 0;
+#endif
   auto compute_stage = [&](const StageRegs<GPT, KSN>& S) {
     if (cj >= nv) return;
     const char* ab = abase + cs * slice_step;
+#ifdef NAD_PHASE_TRACE
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const unsigned long long tr0 = wall_clock64();
+#endif
     stage_mac<BITS, GPT, ASYM, KSN, ST, false>(S, dq, ab, ab, [](int i) { return i * KT * 2; }, a.scale_t, ssh, acc);
+#ifdef NAD_PHASE_TRACE
+    {
+      const int sink = __builtin_amdgcn_readfirstlane(__float_as_int(acc[0]));  // the last MFMA's result has landed
+      asm volatile("" ::"s"(sink));
+      const unsigned long long d = wall_clock64() - tr0;
+      if (tr_k == 0) tr_first = d;
+      else tr_later += d;
+      tr_k++;
+    }
+#endif
     cq += NW;
     cs++;
     if (cq >= nsl) {  // this wave's last slice of stripe cj: publish its partial (row 0 + row 8 = hi + lo)
@@ -780,7 +816,7 @@ __device__ __forceinline__ void m1_stream(const typename P::Args& a, int lane, i
       if constexpr (HL) {
         r += __shfl_down(r, 32, 64);
       }
-      if (lane < 16) part[(size_t(cj) * 16 + lane) * NW + wave] = r;  // [nv][16 columns][NW]: a column's slots together
+      if (lane < 16) part[(size_t(cj) * 16 + lane) * PS + wave] = r;  // [nv][16 columns][PS]: a column's slots together
       acc = f4_t{0.f, 0.f, 0.f, 0.f};
       cq = wave;
       cs = 0;
@@ -795,6 +831,13 @@ __device__ __forceinline__ void m1_stream(const typename P::Args& a, int lane, i
       P::template load<GPT, ASYM, KSN>(a, S[i], lc, nv, nsl, wave, NW, v0, lane, vs);
     }
   }
+#ifdef NAD_PHASE_TRACE
+  if (threadIdx.x == 0 && blockIdx.x < kTraceMaxWg) {
+    nad_trace_buf[5][blockIdx.x] = tr_first;
+    nad_trace_buf[6][blockIdx.x] = tr_later;
+    nad_trace_buf[7][blockIdx.x] = tr_k;
+  }
+#endif
   NAD_TRACE_MAX(2);
   __syncthreads();
 }
@@ -826,7 +869,7 @@ __device__ __forceinline__ void m1_body(GemvArgs& a, int bid) {
   const int vpu = a.dual ? 2 : 1;
   const int v0 = u0 * vpu, nv = (u1 - u0) * vpu;
   float* part = reinterpret_cast<float*>(smem + a.part_off);  // [nv][16 columns][NW]
-  m1_stream<M1General, BITS, GPT, AT, ASYM, KSN, SPW, NST, ST>(a, lane, wave, NW, nsl, v0, nv, wave >= nsl, part);
+  m1_stream<M1General, BITS, GPT, AT, ASYM, KSN, SPW, NST, ST>(a, lane, wave, NW, nsl, v0, nv, wave >= nsl, part, NW);
 
   // 4) sum each stripe's wave slots in wave order and apply the epilogue
   const int nout = (u1 - u0) * 16;
@@ -879,7 +922,7 @@ __device__ __forceinline__ void m1_body(GemvArgs& a, int bid) {
       float y[2] = {0.f, 0.f};
 #pragma unroll
       for (int h = 0; h < 2; h++)
-        if (h < vpu) y[h] = reduce16(part + (size_t(p * vpu + h) * 16 + nn) * 16);
+        if (h < vpu) y[h] = reduce_fixed<16>(part + (size_t(p * vpu + h) * 16 + nn) * 16);
       emit(p, nn, y);
     }
     NAD_TRACE(3);
@@ -916,13 +959,17 @@ __global__ __launch_bounds__(1024) void woq_gemv_m1_dual_kernel(GemvArgs a, Gemv
 // ------------------------------------------------------------------------------------------------ M = 1, specialised
 // The same stream and the same sums as m1_body for the launches a decode token is made of, with the code a launch runs
 // where no memory latency hides it cut down (tools/gemv_path_bytes.py prints it per instantiation):
-//   * GemvM1Args instead of GemvArgs: 128 bytes for one weight, read by one batch of scalar loads, every
-//     per-launch constant worked out by the host;
+//   * its own arguments instead of GemvArgs, every per-launch constant worked out by the host: 14 dwords of leading
+//     scalar parameters that arrive in SGPRs at dispatch (kernarg preload, -mllvm -amdgpu-kernarg-preload-count=14 on
+//     this kernel's objects), so the path to the first loads waits for no scalar load, and a remainder struct read by
+//     one batch of scalar loads behind them;
 //   * NWT, the weights of the launch, at compile time: 1 (no stripe -> weight lookup at all), 3 (fused QKV) or
 //     2 = the {gate, up} pair, which also fixes the epilogue: a plain store for 1 and 3, SiLU(gate) * up for 2.  Every
 //     other epilogue stays on woq_gemv_m1_kernel with its runtime switch;
-//   * L16, whether the launch reduces 16 slots per column (16 waves with a K-slice each), at compile time: one reduce
-//     per instantiation, straight after the stream;
+//   * NSC, the slots per column the launch reduces (= its waves, each with a K-slice of every stripe), at compile
+//     time for the counts the token runs at -- 16, and the down projections' 11 and 7 -- so the wave count is a literal
+//     and the reduce is reduce_fixed; 0 = the runtime count (reduce_slots).  One reduce per instantiation, straight
+//     after the stream;
 //   * a stage's loads are never under control flow (past-the-end stages select the out-of-range offset), so nothing
 //     makes hipcc wait for the activation loads before it issues the first weight stage.
 template <int NWT>
@@ -1003,23 +1050,61 @@ struct M1Spec {  // m1_stream's policy for woq_gemv_m1s_kernel
   }
 };
 
-template <int BITS, int GPT, int AT, bool ASYM, int KSN, int SPW, int NST, int ST, int NWT, bool L16>
-__global__ __launch_bounds__((m1_max_threads<GPT, KSN>())) void woq_gemv_m1s_kernel(GemvM1Args<NWT> a) {
+// The leading scalar parameters are the preloaded ones (woq_kernels.h has the layout); a, the view the stream and the
+// tail work on, is put together from them and from the remainder r.  Nothing on the way to the first loads of a
+// one-weight or pair launch reads r (the pair's first stage is a gate stripe: weight 0); the 3-weight form's stripe ->
+// weight select does, behind the activation loads.
+template <int BITS, int GPT, int AT, bool ASYM, int KSN, int SPW, int NST, int ST, int NWT, int NSC>
+__global__ __launch_bounds__((m1_max_threads<GPT, KSN>())) void woq_gemv_m1s_kernel(
+    const void* A, const void* tiles0, const void* scales0, const void* tiles1, const void* scales1, int a_bytes,
+    uint32_t uqr, uint32_t geom, int ns0, GemvM1Rest<NWT> r) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   static_assert(NWT >= 1 && NWT <= 3, "1 weight, the {gate, up} pair, or 3 weights");
+  static_assert(NSC == 0 || (NSC >= 4 && NSC <= 16), "slots per column: 0 = by the launch");
   constexpr int VPU = NWT == 2 ? 2 : 1;
+  GemvM1Args<NWT> a;
+  a.A = A;
+  a.a_bytes = a_bytes;
+  a.u_q = int(uqr & 0xFFFFu);
+  a.u_r = int(uqr >> 16);
+  a.nt = int(geom & ((1u << kM1GeomNgShift) - 1));
+  a.ng = int((geom >> kM1GeomNgShift) & ((1u << (kM1GeomTpgShift - kM1GeomNgShift)) - 1));
+  a.tpg_shift = int((geom >> kM1GeomTpgShift) & 31u);
+  a.scale_t = int((geom >> kM1GeomScaleShift) & 3u);
+  a.nw = int(geom >> kM1GeomWavesShift);
+  a.nsl = (a.nt + KSN - 1) / KSN;
+  a.part_off = r.part_off;
+  a.dq_mask = r.dq_mask;
+  a.dq_magic = r.dq_magic;
+  a.sb1 = r.sb1;
+  a.sb2 = r.sb2;
+  a.aux = r.aux;
+#pragma unroll
+  for (int i = 0; i < NWT; i++) {
+    const int ns = i == 0 || NWT == 2 ? ns0 : r.ns[i];
+    a.w[i].tiles = i == 0 ? tiles0 : (i == 1 ? tiles1 : r.tiles2);
+    a.w[i].scales = i == 0 ? scales0 : (i == 1 ? scales1 : r.scales2);
+    a.w[i].zps = r.zps[i];
+    a.w[i].tiles_bytes = (ns * a.nt) << 10;
+    a.w[i].scales_bytes = (ns * a.ng) << (a.scale_t == kScaleF32 ? 6 : 5);
+    a.w[i].zps_bytes = (ns * a.ng) << 4;
+    a.w[i].n = r.n[i];
+    a.w[i].out = r.out[i];
+  }
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6));
-  const int NW = L16 ? 16 : a.nw;
+  // NSC: the launch has NSC waves and every one of them owns a K-slice of every stripe, so a column has NSC slots
+  const int NW = NSC ? NSC : a.nw;
+  const int PS = NSC ? (NSC + 3) & ~3 : NW;  // whole 16-B LDS reads per column
   const int nsl = a.nsl;
   NAD_TRACE(0);
   const int bid = int(blockIdx.x);
   const int u0 = bid * a.u_q + min(bid, a.u_r);
   const int nu = a.u_q + (bid < a.u_r ? 1 : 0);
   const int v0 = u0 * VPU, nv = nu * VPU;
-  const bool idle = !L16 && wave >= nsl;  // L16: every wave owns a slice
-  float* part = reinterpret_cast<float*>(smem + a.part_off);  // [nv][16 columns][NW]
-  m1_stream<M1Spec<NWT>, BITS, GPT, AT, ASYM, KSN, SPW, NST, ST>(a, lane, wave, NW, nsl, v0, nv, idle, part);
+  const bool idle = NSC == 0 && wave >= nsl;
+  float* part = reinterpret_cast<float*>(smem + a.part_off);  // [nv][16 columns][PS]
+  m1_stream<M1Spec<NWT>, BITS, GPT, AT, ASYM, KSN, SPW, NST, ST>(a, lane, wave, NW, nsl, v0, nv, idle, part, PS);
 
   // 4) sum each stripe's wave slots in wave order (m1_body's order exactly), then the store
   const int nout = nu * 16;
@@ -1028,8 +1113,8 @@ __global__ __launch_bounds__((m1_max_threads<GPT, KSN>())) void woq_gemv_m1s_ker
     float y[VPU];
 #pragma unroll
     for (int h = 0; h < VPU; h++) {
-      if constexpr (L16)
-        y[h] = reduce16(part + (size_t(p * VPU + h) * 16 + nn) * 16);
+      if constexpr (NSC != 0)
+        y[h] = reduce_fixed<NSC>(part + (size_t(p * VPU + h) * 16 + nn) * PS);
       else
         y[h] = reduce_slots(part + (size_t(p * VPU + h) * 16 + nn) * NW, min(NW, nsl));
     }
@@ -1129,19 +1214,8 @@ static hipError_t gemv_m1_launch4(const GemvArgs& a, dim3 g, dim3 b, size_t lds,
 // but {none, SiLU*mul}, two weights, a batch, and the geometries left out below -- and woq_gemv_m1_kernel takes it.
 // e == nullptr: a dry run, nothing is launched.
 template <int NWT>
-static GemvM1Args<NWT> m1s_args(const GemvArgs& a, int ksn, int waves) {
-  GemvM1Args<NWT> c{};
-  const int esz = a.act_t == kActF32 ? 4 : 2, ssz = a.scale_t == kScaleF32 ? 4 : 2;
-  c.A = a.A;
-  c.a_bytes = a.K * esz;
-  c.nsl = (a.nt + ksn - 1) / ksn;
-  c.u_q = a.u_q;
-  c.u_r = a.u_r;
-  c.nt = a.nt;
-  c.ng = a.ng;
-  c.tpg_shift = a.tpg_shift;
-  c.scale_t = a.scale_t;
-  c.nw = waves;
+static GemvM1Rest<NWT> m1s_rest(const GemvArgs& a) {
+  GemvM1Rest<NWT> c{};
   c.part_off = a.part_off;
   c.dq_mask = a.dq_mask;
   c.dq_magic = a.dq_magic;
@@ -1149,58 +1223,74 @@ static GemvM1Args<NWT> m1s_args(const GemvArgs& a, int ksn, int waves) {
   c.sb2 = a.stripe_base[2];
   for (int i = 0; i < NWT; i++) {
     const SkinnyWeight& w = a.w[i];
-    c.w[i].tiles = w.tiles;
-    c.w[i].scales = w.scales;
-    c.w[i].zps = w.zps;
-    c.w[i].tiles_bytes = w.ns * a.nt * 1024;
-    c.w[i].scales_bytes = w.ns * a.ng * 16 * ssz;
-    c.w[i].zps_bytes = w.ns * a.ng * 16;
-    c.w[i].n = w.n;
-    c.w[i].out = w.out;
+    c.ns[i] = w.ns;
+    c.zps[i] = w.zps;
+    c.n[i] = w.n;
+    c.out[i] = w.out;
   }
+  c.tiles2 = NWT > 2 ? a.w[2].tiles : nullptr;
+  c.scales2 = NWT > 2 ? a.w[2].scales : nullptr;
   c.aux = a.aux;
   return c;
 }
-template <int BITS, int GPT, int AT, bool ASYM, int KSN, int SPW, int NST, int ST, int NWT, bool L16>
+// whether the launch fits the packed leading parameters (field widths of uqr / geom, one stripe count for the pair)
+static bool m1s_packable(const GemvArgs& a, int nwt, int waves) {
+  if (a.u_q < 0 || a.u_q > 0xFFFF || a.u_r < 0 || a.u_r > 0xFFFF) return false;
+  if (a.nt >= (1 << kM1GeomNgShift) || a.ng >= (1 << (kM1GeomTpgShift - kM1GeomNgShift))) return false;
+  if (a.tpg_shift < 0 || a.tpg_shift > 31 || a.scale_t < 0 || a.scale_t > 3 || waves > 16) return false;
+  return nwt != 2 || a.w[0].ns == a.w[1].ns;
+}
+template <int BITS, int GPT, int AT, bool ASYM, int KSN, int SPW, int NST, int ST, int NWT, int NSC>
 static hipError_t m1s_go(const GemvArgs& a, dim3 g, dim3 b, size_t lds, hipStream_t st) {
-  return launch_big_lds<woq_gemv_m1s_kernel<BITS, GPT, AT, ASYM, KSN, SPW, NST, ST, NWT, L16>>(
-      g, b, lds, st, m1s_args<NWT>(a, KSN, int(b.x / 64)));
+  const int esz = a.act_t == kActF32 ? 4 : 2;
+  const uint32_t uqr = uint32_t(a.u_q) | uint32_t(a.u_r) << 16;
+  const uint32_t geom = uint32_t(a.nt) | uint32_t(a.ng) << kM1GeomNgShift | uint32_t(a.tpg_shift) << kM1GeomTpgShift |
+                        uint32_t(a.scale_t) << kM1GeomScaleShift | uint32_t(b.x / 64) << kM1GeomWavesShift;
+  return launch_big_lds<woq_gemv_m1s_kernel<BITS, GPT, AT, ASYM, KSN, SPW, NST, ST, NWT, NSC>>(
+      g, b, lds, st, a.A, a.w[0].tiles, a.w[0].scales, NWT > 1 ? a.w[1].tiles : nullptr,
+      NWT > 1 ? a.w[1].scales : nullptr, a.K * esz, uqr, geom, a.w[0].ns, m1s_rest<NWT>(a));
 }
 // weights of the launch as woq_gemv_m1s_kernel's NWT (0: not served)
-static int m1s_nwt(const GemvArgs& a) {
+static int m1s_nwt(const GemvArgs& a, int waves) {
   if (a.batch || !a.m1_spec) return 0;
-  if (a.dual) return a.epi == kEpiSiluMul ? 2 : 0;
-  if (a.epi != kEpiNone) return 0;
-  const int nw = 1 + (a.stripe_base[1] != INT_MAX ? 1 : 0) + (a.stripe_base[2] != INT_MAX ? 1 : 0);
-  return nw == 1 || nw == 3 ? nw : 0;
+  int nwt = 0;
+  if (a.dual) {
+    nwt = a.epi == kEpiSiluMul ? 2 : 0;
+  } else if (a.epi == kEpiNone) {
+    const int nw = 1 + (a.stripe_base[1] != INT_MAX ? 1 : 0) + (a.stripe_base[2] != INT_MAX ? 1 : 0);
+    nwt = nw == 1 || nw == 3 ? nw : 0;
+  }
+  return nwt != 0 && m1s_packable(a, nwt, waves) ? nwt : 0;
 }
-// Instantiated: slices of 1 or 2 tiles, one per wave: every weight count, both reduces, two register stages
-// for one weight only (lm_head); 4-tile slices with fewer than 16 slots per column: two per wave for every weight count
-// (two stages: one weight), four per wave for one weight (the long K of a down projection).
+// Instantiated: slices of 1 or 2 tiles, one per wave: every weight count, 16 slots per column or the runtime count,
+// two register stages for one weight only (lm_head); 4-tile slices with fewer than 16 slots per column: two per wave
+// for every weight count (two stages: one weight), four per wave for one weight (the long K of a down projection) --
+// the runtime count, and for one weight the two counts the down projections of the token run at: 11 (Llama, K = 11008:
+// two slices per wave) and 7 (Mistral, K = 14336: four).
 template <int BITS, int GPT, int AT, bool ASYM, int ST>
 static bool m1s_launch3(const GemvArgs& a, dim3 g, dim3 b, size_t lds, hipStream_t st, hipError_t* e) {
-  const int nwt = m1s_nwt(a), waves = int(b.x / 64), ks = lean_ks(a);
+  const int waves = int(b.x / 64), ks = lean_ks(a), nwt = m1s_nwt(a, waves);
   if (nwt == 0) return false;
   const int nsl = (a.nt + ks - 1) / ks;
   const bool l16 = waves == 16 && nsl >= 16;
   const int nst = m1_nst(a, ks, waves);
-#define NAD_M1S(KSN, SPW, NST, NWT, L16)                                                         \
+#define NAD_M1S(KSN, SPW, NST, NWT, NSC)                                                         \
   do {                                                                                           \
-    if (e) *e = m1s_go<BITS, GPT, AT, ASYM, KSN, SPW, NST, ST, NWT, L16>(a, g, b, lds, st);      \
+    if (e) *e = m1s_go<BITS, GPT, AT, ASYM, KSN, SPW, NST, ST, NWT, NSC>(a, g, b, lds, st);      \
     return true;                                                                                 \
   } while (0)
 #define NAD_M1S_NARROW(KSN)                               \
   do {                                                    \
     if (nst == 1) {                                       \
-      if (nwt == 1 && l16) NAD_M1S(KSN, 1, 1, 1, true);   \
-      if (nwt == 1) NAD_M1S(KSN, 1, 1, 1, false);         \
-      if (nwt == 2 && l16) NAD_M1S(KSN, 1, 1, 2, true);   \
-      if (nwt == 2) NAD_M1S(KSN, 1, 1, 2, false);         \
-      if (nwt == 3 && l16) NAD_M1S(KSN, 1, 1, 3, true);   \
-      if (nwt == 3) NAD_M1S(KSN, 1, 1, 3, false);         \
+      if (nwt == 1 && l16) NAD_M1S(KSN, 1, 1, 1, 16);     \
+      if (nwt == 1) NAD_M1S(KSN, 1, 1, 1, 0);             \
+      if (nwt == 2 && l16) NAD_M1S(KSN, 1, 1, 2, 16);     \
+      if (nwt == 2) NAD_M1S(KSN, 1, 1, 2, 0);             \
+      if (nwt == 3 && l16) NAD_M1S(KSN, 1, 1, 3, 16);     \
+      if (nwt == 3) NAD_M1S(KSN, 1, 1, 3, 0);             \
     } else if (nwt == 1) {                                \
-      if (l16) NAD_M1S(KSN, 1, 2, 1, true);               \
-      NAD_M1S(KSN, 1, 2, 1, false);                       \
+      if (l16) NAD_M1S(KSN, 1, 2, 1, 16);                 \
+      NAD_M1S(KSN, 1, 2, 1, 0);                           \
     }                                                     \
     return false;                                         \
   } while (0)
@@ -1208,15 +1298,19 @@ static bool m1s_launch3(const GemvArgs& a, dim3 g, dim3 b, size_t lds, hipStream
   if (ks == 2) NAD_M1S_NARROW(2);
   if (l16 || (GPT != 1 && waves > 8)) return false;
   if (lean_spw(a) == 4) {
-    if (nwt == 1 && nst == 1) NAD_M1S(KS, 4, 1, 1, false);
+    if (nwt == 1 && nst == 1 && waves == 7 && nsl >= 7) NAD_M1S(KS, 4, 1, 1, 7);
+    if (nwt == 1 && nst == 1) NAD_M1S(KS, 4, 1, 1, 0);
     return false;
   }
   if (nst == 1) {
-    if (nwt == 1) NAD_M1S(KS, 2, 1, 1, false);
-    if (nwt == 2) NAD_M1S(KS, 2, 1, 2, false);
-    NAD_M1S(KS, 2, 1, 3, false);
+    if constexpr (GPT == 1) {  // 11 waves: groups of a whole tile or coarser only
+      if (nwt == 1 && waves == 11 && nsl >= 11) NAD_M1S(KS, 2, 1, 1, 11);
+    }
+    if (nwt == 1) NAD_M1S(KS, 2, 1, 1, 0);
+    if (nwt == 2) NAD_M1S(KS, 2, 1, 2, 0);
+    NAD_M1S(KS, 2, 1, 3, 0);
   }
-  if (nwt == 1) NAD_M1S(KS, 2, 2, 1, false);
+  if (nwt == 1) NAD_M1S(KS, 2, 2, 1, 0);
   return false;
 #undef NAD_M1S_NARROW
 #undef NAD_M1S
@@ -1311,7 +1405,8 @@ size_t gemv_lds_layout(GemvArgs& a, int bits, int waves, int grid) {
   if (lean_ok(a, bits, waves)) {  // the M = 1 kernels: per-wave rows, then the partial slots [nv][16 columns][waves]
     const int upw = (a.units + grid - 1) / grid;
     a.part_off = waves * lean_wave_lds(bits, lean_ks(a), lean_spw(a));
-    return size_t(a.part_off) + size_t(upw) * (a.dual ? 2 : 1) * waves * 16 * 4;
+    // ... with room for the slot stride of woq_gemv_m1s_kernel's fixed counts: the waves rounded up to 4
+    return size_t(a.part_off) + size_t(upw) * (a.dual ? 2 : 1) * ((waves + 3) & ~3) * 16 * 4;
   }
   const int KT = bits == 4 ? 128 : (bits == 2 ? 256 : 64);
   const int R = a.act_t == kActF16 ? a.M : 2 * a.M;

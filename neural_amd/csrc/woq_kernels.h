@@ -145,10 +145,34 @@ struct GemvArgs {
   int m1_spec;                // M = 1 launches may take woq_gemv_m1s_kernel (NAD_GEMV_M1_SPEC; 0: always the kernel above)
 };
 
-// The argument block of woq_gemv_m1s_kernel: only what that kernel reads, in the order it reads it, with everything
-// that is constant per launch worked out by launch_gemv (buffer sizes, K-slices per stripe, units per workgroup).  A
-// one-weight launch is 120 bytes -- two scalar-cache lines, fetched by one batch of scalar loads -- where GemvArgs is
-// 440.  NWS: weights in the launch (1; 3 = fused QKV; 2 = the {gate, up} pair of the SiLU*mul epilogue).
+// The arguments of woq_gemv_m1s_kernel: only what that kernel reads, with everything that is constant per launch
+// worked out by launch_gemv (K-slices per stripe, units per workgroup).  NWS: weights in the launch (1; 3 = fused QKV;
+// 2 = the {gate, up} pair of the SiLU*mul epilogue).
+//
+// The kernel takes them in two parts.  What the path to the first loads needs comes first, as plain scalar parameters
+// of 14 dwords in all, which gfx950 delivers in SGPRs at dispatch (kernarg preload: the wave starts with them instead
+// of waiting for a scalar load): A, the tiles / scales pointers of weights 0 and 1, and four dwords
+//   a_bytes
+//   uqr    u_q | u_r << 16
+//   geom   nt | ng << 9 | tpg_shift << 20 | scale_t << 25 | waves << 27
+//   ns0    stripes of weight 0 (the pair: of both); the buffer-resource sizes follow from it
+// (m1s_packable() in woq_gemv.hip holds the field widths).  Everything else is the by-value GemvM1Rest that comes last
+// and is read by scalar loads behind the first loads, as before.  GemvM1Args is what the kernel puts the two together
+// into: the view its stream and tail work on, never a kernel argument itself.
+constexpr int kM1GeomNgShift = 9, kM1GeomTpgShift = 20, kM1GeomScaleShift = 25, kM1GeomWavesShift = 27;
+template <int NWS>
+struct GemvM1Rest {
+  int part_off;         // LDS byte offset of the partial-sum slots
+  uint32_t dq_mask, dq_magic;
+  int sb1, sb2;         // NWS == 3: first virtual stripe of weights 1 and 2
+  int ns[3];            // NWS == 3: stripes of each weight (weights 1 and 2's resource sizes)
+  const void* tiles2;   // NWS == 3: weight 2
+  const void* scales2;
+  const int8_t* zps[NWS];
+  int n[NWS];           // output columns (tail)
+  float* out[NWS];      // (tail)
+  float* aux;           // NWS == 2: optional silu(gate) output (tail)
+};
 struct GemvM1Weight {
   const void* tiles;
   const void* scales;

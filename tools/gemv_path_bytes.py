@@ -6,6 +6,10 @@ every dispatch): everything before the first weight-tile load, and everything af
 cross-compiles csrc/woq_gemv.hip for gfx950 (device code only, just the named instantiations, no launchers), disassembles
 the object and prints, per kernel:
 
+  preload          dwords of leading kernel arguments the hardware delivers in SGPRs at dispatch (the kernel
+                   descriptor's kernarg preload length).  Where it is not 0 the code begins with a 256-byte
+                   compatibility block (scalar loads of those arguments, a wait, a branch) that hardware with preload
+                   support skips: the walk below starts at the real entry behind it
   pro_ins / pro_B  instructions and code bytes from the entry to the first non-temporal tile load on the live path
                    (the shortest path through the control-flow graph to a `buffer_load_dwordx4 ... offen ... nt`
                    whose offset register does not hold the out-of-range constant of a two-armed stage load's dead arm)
@@ -26,6 +30,7 @@ import difflib
 import os
 import re
 import shutil
+import struct
 import subprocess
 import sys
 import tempfile
@@ -41,11 +46,13 @@ def generic(bits, gpt, at, asym, ksn, spw, batch, nst, st=-1):
         "GemvArgs"
 
 
-def spec(bits, gpt, at, asym, ksn, spw, nst, st, nwt, l16):
-    """woq_gemv_m1s_kernel: compact argument block, weight count / reduce / epilogue class at compile time."""
+def spec(bits, gpt, at, asym, ksn, spw, nst, st, nwt, nsc):
+    """woq_gemv_m1s_kernel: preloaded leading arguments, weight count / slots per column / epilogue class at compile
+    time."""
     b = lambda v: "true" if v else "false"
-    return "woq_gemv_m1s_kernel<%d,%d,%d,%s,%d,%d,%d,%d,%d,%s>" % (bits, gpt, ACT[at], b(asym), ksn, spw, nst, st, nwt,
-                                                                   b(l16)), "GemvM1Args<%d>" % nwt
+    return "woq_gemv_m1s_kernel<%d,%d,%d,%s,%d,%d,%d,%d,%d,%d>" % (bits, gpt, ACT[at], b(asym), ksn, spw, nst, st, nwt,
+                                                                   nsc), \
+        "const void*, const void*, const void*, const void*, const void*, int, uint32_t, uint32_t, int, GemvM1Rest<%d>" % nwt
 
 
 # name -> (kernel template-id, argument type).  Llama-2-7B int4 g128 decode: QKV (3 weights), O (1), gate/up (pair) run
@@ -56,12 +63,12 @@ def kernel_sets(legacy):
                 ("down", generic(4, 1, "f32", False, 4, 2, False, 1))]
         rest = [("lm_head", generic(4, 1, "f32", False, 2, 1, False, 2))]
     else:
-        head = [("o (1 weight)", spec(4, 1, "f32", False, 2, 1, 1, -1, 1, True)),
-                ("down", spec(4, 1, "f32", False, 4, 2, 1, -1, 1, False))]
-        rest = [("qkv (3 weights)", spec(4, 1, "f32", False, 2, 1, 1, -1, 3, True)),
-                ("gate/up (pair)", spec(4, 1, "f32", False, 2, 1, 1, -1, 2, True)),
-                ("lm_head", spec(4, 1, "f32", False, 2, 1, 2, -1, 1, True)),
-                ("asym (spec)", spec(4, 1, "f32", True, 2, 1, 1, -1, 1, True)),
+        head = [("o (1 weight)", spec(4, 1, "f32", False, 2, 1, 1, -1, 1, 16)),
+                ("down", spec(4, 1, "f32", False, 4, 2, 1, -1, 1, 11))]
+        rest = [("qkv (3 weights)", spec(4, 1, "f32", False, 2, 1, 1, -1, 3, 16)),
+                ("gate/up (pair)", spec(4, 1, "f32", False, 2, 1, 1, -1, 2, 16)),
+                ("lm_head", spec(4, 1, "f32", False, 2, 1, 2, -1, 1, 16)),
+                ("asym (spec)", spec(4, 1, "f32", True, 2, 1, 1, -1, 1, 16)),
                 ("generic qkv/o/gate-up", generic(4, 1, "f32", False, 2, 1, False, 1)),
                 ("generic down", generic(4, 1, "f32", False, 4, 2, False, 1))]
     rest += [("asym/bf16-scale (generic)", generic(4, 1, "f32", True, 2, 1, False, 1)),
@@ -92,8 +99,9 @@ def compile_kernels(source, kernels, workdir, arch="gfx950"):
         f.write("}\n")
     obj = os.path.join(workdir, "gemv_only.o")
     # GEMV_PART=99: no launcher section (they would instantiate every kernel of the object)
+    # the preload flag of the Makefile's GEMV_PRELOAD (kernels whose first parameter is a struct keep length 0)
     cmd = [hipcc_path(), "--offload-arch=" + arch, "--cuda-device-only", "--no-gpu-bundle-output", "-O3", "-std=c++17",
-           "-DGEMV_PART=99", "-I", os.path.dirname(os.path.abspath(source)), "-Wno-unused-function", "-c", wrap, "-o", obj]
+           "-mllvm", "-amdgpu-kernarg-preload-count=14", "-DGEMV_PART=99", "-I", os.path.dirname(os.path.abspath(source)), "-Wno-unused-function", "-c", wrap, "-o", obj]
     subprocess.run(cmd, check=True)
     return obj
 
@@ -137,10 +145,35 @@ def metadata(obj):
     return res
 
 
-def analyse(ins):
-    """Path figures of one kernel's instruction list."""
+def preload_lengths(obj):
+    """{mangled kernel name: kernarg preload length in dwords} from the kernel descriptors (the <name>.kd objects: 64
+    bytes, the preload field is the u16 at byte 58, length in its bits 0-6)."""
+    with open(obj, "rb") as f:
+        d = f.read()
+    shoff, = struct.unpack_from("<Q", d, 0x28)
+    shentsize, shnum = struct.unpack_from("<HH", d, 0x3A)
+    secs = [struct.unpack_from("<IIQQQQIIQQ", d, shoff + i * shentsize) for i in range(shnum)]
+    res = {}
+    for sec in secs:
+        if sec[1] != 2:  # SHT_SYMTAB
+            continue
+        stroff = secs[sec[6]][4]
+        for o in range(sec[4], sec[4] + sec[5], 24):
+            name_off, _, _, shndx, value, size = struct.unpack_from("<IBBHQQ", d, o)
+            name = d[stroff + name_off:d.index(b"\0", stroff + name_off)].decode()
+            if not name.endswith(".kd") or not 0 < shndx < shnum:
+                continue
+            at = secs[shndx][4] + value - secs[shndx][3]
+            res[name[:-3]] = struct.unpack_from("<H", d, at + 58)[0] & 0x7F
+    return res
+
+
+def analyse(ins, preload=0):
+    """Path figures of one kernel's instruction list; preload: its kernarg preload length."""
     by_addr = {a: i for i, (a, _, _, _) in enumerate(ins)}
     base = ins[0][0]
+    # the real entry: behind the 256-byte block for hardware without kernarg preload
+    entry = by_addr[base + 256] if preload else 0
 
     def target(i):
         a, sz, mn, ops = ins[i]
@@ -164,7 +197,7 @@ def analyse(ins):
 
     # shortest path (in instructions) from the entry to a live tile load: Dijkstra over instruction indices
     import heapq
-    dist, prev, heap, goal = {0: 0}, {}, [(0, 0)], None
+    dist, prev, heap, goal = {entry: 0}, {}, [(0, entry)], None
     while heap:
         d, i = heapq.heappop(heap)
         if d > dist.get(i, 1 << 60):
@@ -189,10 +222,10 @@ def analyse(ins):
                 dist[j] = d + 1
                 prev[j] = i
                 heapq.heappush(heap, (d + 1, j))
-    r = {"pro_ins": -1, "pro_B": -1, "lgkm": -1, "vm": -1}
+    r = {"preload": preload, "pro_ins": -1, "pro_B": -1, "lgkm": -1, "vm": -1}
     if goal is not None:
         path, i = [], goal
-        while i != 0:
+        while i != entry:
             i = prev[i]
             path.append(i)
         path.reverse()
@@ -222,6 +255,7 @@ def report(source, kernels, arch="gfx950", keep=None, with_code=False):
         obj = compile_kernels(source, [k for _, k in kernels], work, arch)
         funcs = disassemble(obj)
         meta = metadata(obj)
+        pre = preload_lengths(obj)
         rows = []
         for label, (tid, _) in kernels:
             key = squash(tid)
@@ -238,12 +272,12 @@ def report(source, kernels, arch="gfx950", keep=None, with_code=False):
             sym = [s for s in funcs if same(s)]
             if len(sym) != 1:
                 raise RuntimeError("kernel %s: %d symbols match" % (tid, len(sym)))
-            fig = analyse(funcs[sym[0]])
-            rows.append((label, tid, fig, sym[0]))
+            rows.append([label, tid, None, sym[0]])
         # metadata entries come in the order of the kernels' definition = the order of explicit instantiation
         if len(meta) == len(rows):
             order = sorted(range(len(rows)), key=lambda i: funcs[rows[i][3]][0][0])
             for mi, ri in enumerate(order):
+                rows[ri][2] = analyse(funcs[rows[ri][3]], pre[meta[mi]["name"]])
                 rows[ri][2].update(sgpr=int(meta[mi]["sgpr_count"]), vgpr=int(meta[mi]["vgpr_count"]),
                                    scratch=int(meta[mi]["private_segment_fixed_size"]))
         else:
@@ -256,7 +290,7 @@ def report(source, kernels, arch="gfx950", keep=None, with_code=False):
             shutil.rmtree(work, ignore_errors=True)
 
 
-COLS = ["pro_ins", "pro_B", "lgkm", "vm", "tail_B", "barriers", "total_ins", "total_B", "sgpr", "vgpr", "scratch"]
+COLS = ["preload", "pro_ins", "pro_B", "lgkm", "vm", "tail_B", "barriers", "total_ins", "total_B", "sgpr", "vgpr", "scratch"]
 
 
 def main():

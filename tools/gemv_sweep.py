@@ -130,6 +130,14 @@ def main():
                 print(f"    main loop         {q(s2 - s1)}")
                 print(f"    reduce+epilogue   {q(s3 - s2)}")
                 print(f"    wg end offset     {q(s3 - t0)}")
+                # the M = 1 kernels: wave 0's arithmetic per stage, each stage timed from an explicit wait for its
+                # loads -- the first one (its code is executed for the first time) against the later ones
+                first, later, nst = (buf[i, :grid].astype(np.int64) for i in (5, 6, 7))
+                if (nst > 0).any():
+                    print(f"    first stage arith {q(first[nst > 0])}")
+                if (nst > 1).any():
+                    m = nst > 1
+                    print(f"    later stage arith {q(later[m] / (nst[m] - 1))}  (stages per wave {int(nst.max())})")
         set_env(None)
         del ws
 
