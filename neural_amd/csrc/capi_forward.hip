@@ -454,6 +454,17 @@ static int splitk_plan(const DeviceWeight& w, int m, int* ktiles, int bm = 256) 
   return s;
 }
 
+// The slabs of a split-K launch (ks runs of ktiles K tiles; launch_splitk_reduce sums them): ks x m fp32 rows in the
+// stream's workspace (stream-ordered reuse) after the caller's a16 bytes, the fp16 activations' room; false: none
+static bool splitk_slabs(GemmArgs& a, const DeviceWeight& w, int m, int ks, int ktiles, size_t a16, hipStream_t st) {
+  a.ksplit = ks;
+  a.ktiles = ktiles;
+  a.ldp = (w.n + 3) / 4 * 4;
+  char* base = static_cast<char*>(workspace_for(a16 + size_t(ks) * m * a.ldp * 4, st));
+  if (base) a.part = reinterpret_cast<float*>(base + a16);
+  return base != nullptr;
+}
+
 // Geometry of a mid-M launch: stripes per workgroup, its waves, stages per wave (mid_geometry), stripe groups, K runs
 struct MidGeom {
   int sps, nw, spw, nsg, ks;
@@ -493,6 +504,7 @@ static int run_mid(const Act& x, const DeviceWeight& w, const Out& o, const Epi&
   const int esz = x.t == kActF32 ? 4 : 2;
   if (uint64_t(m) * x.ld * esz >= (1ull << 31) || uint64_t(w.ns) * w.nt * 1024 >= (1ull << 31)) return 0;
   const int rf = (m + 15) / 16;
+  if (rf > 4) return 0;  // NAD_MID_MAX_M above 64: mid_geometry has no shape for more than 4 row fragments
   MidGeom g = mid_plan(w, gpt, x.t, rf, kn.mid_wide == 1);
   // from 8 rows of fp32 / bf16 activations (the GEMV stages them as two fp16 rows each) the mid-M kernel beats the
   // stripe-stream GEMV: K = N = 4096 M = 16 8.3 vs 10.1 us (fp16), 9.0 vs 12.7 (fp32); N = 11008 fp32 M = 16 17.7 vs
@@ -516,14 +528,9 @@ static int run_mid(const Act& x, const DeviceWeight& w, const Out& o, const Epi&
   a.tpg_shift = tpg == 0 ? 31 : __builtin_ctz(unsigned(tpg));
   a.w = view(w, o.p, o.ld, e);
   if (ks > 1) {
-    a.ksplit = ks;
-    a.ktiles = ktiles;
-    a.ldp = (w.n + 3) / 4 * 4;
-    if (uint64_t(ks) * m * a.ldp * 4 >= (1ull << 31)) return 0;
+    if (uint64_t(ks) * m * ((w.n + 3) / 4 * 4) * 4 >= (1ull << 31)) return 0;
     const size_t a16 = (size_t(m) * ((size_t(x.k) + 255) / 256 * 256) * 2 + 255) / 256 * 256;  // an fp16 copy's room
-    char* base = static_cast<char*>(workspace_for(a16 + size_t(ks) * m * a.ldp * 4, st));
-    if (!base) return -1;
-    a.part = reinterpret_cast<float*>(base + a16);
+    if (!splitk_slabs(a, w, m, ks, ktiles, a16, st)) return -1;
   } else {
     a.ktiles = w.nt;
   }
@@ -644,15 +651,8 @@ static int run_gemm(const Act& x, const DeviceWeight& w, const Out& o, const Epi
   int ktiles = w.nt;
   const int ks = !g2 ? splitk_plan(w, m, &ktiles, bm) : 1;
   if (ks > 1 && kn.gemm4_ksw == 2) a.ksw = 0;  // auto KSW was measured on whole-K launches only
-  if (ks > 1) {  // partials after the fp16 activations in the same workspace (stream-ordered reuse)
-    a.ksplit = ks;
-    a.ktiles = ktiles;
-    a.ldp = (w.n + 3) / 4 * 4;
-    const size_t a16 = (size_t(m) * w.nt * k_tile(w) * 2 + 255) / 256 * 256;
-    char* base = static_cast<char*>(workspace_for(a16 + size_t(ks) * m * a.ldp * 4, st));
-    if (!base) return -1;
-    a.part = reinterpret_cast<float*>(base + a16);
-  }
+  // partials after the fp16 activations
+  if (ks > 1 && !splitk_slabs(a, w, m, ks, ktiles, (size_t(m) * w.nt * k_tile(w) * 2 + 255) / 256 * 256, st)) return -1;
   const int tiles = ((m + bm - 1) / bm) * ((w.n + 127) / 128);
   // split K: every run of a tile and the reduce of its slabs on one XCD (slabs read back from that XCD's L2): K = N =
   // 4096 M = 128 18.6 -> 15.9 us, M = 96 17.2 -> 14.8 (profiles/r06_gemm7_xcd_splitk_ab.txt)

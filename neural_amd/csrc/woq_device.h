@@ -1,6 +1,6 @@
-// woq_device.h -- device helpers shared by the gfx950 WOQ kernels (woq_kernels.hip, woq_gemv.hip): fp16/bf16 bit
-// conversions, the 0x6400 magic-number dequantization of one MFMA B fragment, activation loaders and the epilogue
-// activations (bestla_common.hpp:121-216).
+// woq_device.h -- device helpers shared by every gfx950 WOQ kernel: fp16/bf16 bit conversions, the 0x6400 magic-number
+// dequantization of one MFMA B fragment, buffer resources, activation loaders and the epilogue activations
+// (bestla_common.hpp:121-216).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -31,30 +31,92 @@ __device__ __forceinline__ h2_t as_h2(uint32_t v) { return __builtin_bit_cast(h2
 
 // (x & m) | c as ONE v_and_or_b32 (hipcc emits v_and_b32 + v_or_b32 for the C form: the literal mask and magic cannot
 // share a VOP3 on gfx9; here the mask sits in an SGPR and the magic in a VGPR)
-__device__ __forceinline__ uint32_t dq_and_or(uint32_t x, uint32_t m, uint32_t c) {
+__device__ __forceinline__ uint32_t and_or(uint32_t x, uint32_t m, uint32_t c) {
   uint32_t r;
   asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(r) : "v"(x), "s"(m), "v"(c));
   return r;
 }
+__device__ __forceinline__ h2_t splat(float v) {
+  h2_t r;
+  r[0] = _Float16(v);
+  r[1] = _Float16(v);
+  return r;
+}
+__device__ __forceinline__ h8_t pack_h8(h2_t p0, h2_t p1, h2_t p2, h2_t p3) {
+  h8_t r;
+  r[0] = p0[0];
+  r[1] = p0[1];
+  r[2] = p1[0];
+  r[3] = p1[1];
+  r[4] = p2[0];
+  r[5] = p2[1];
+  r[6] = p3[0];
+  r[7] = p3[1];
+  return r;
+}
 
-// One MFMA step's B fragment (8 fp16 = exact integers q - zp) from the packed dwords.
-//   c2 = (-(1024 + bias + zp)) broadcast as half2.
+// A raw buffer resource over `bytes` bytes at p (-1: unbounded), and a buffer offset past every resource: the load
+// returns 0 and touches no memory
+constexpr int kOOB = 0x7FFF0000;
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const void* p, int bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, bytes, 0x00020000);
+}
+
+// The dequantization cores: one MFMA step's B fragment, 8 exact integer fp16 (q - bias - zp), element order of
+// woq_layout.h.  The 0x6400 magic leaves the ten mantissa bits free, so a field or'ed into it reads 1024 + its value.
+// `fold` finishes each pair as it is formed: nothing (NoFold), or the group scale of the folded GEMMs (Fold: q * s
+// rounded once to fp16).  hipcc's schedule follows the statement order, so the pairs are finished one by one.
+struct NoFold {
+  __device__ __forceinline__ h2_t operator()(h2_t p) const { return p; }
+};
+struct Fold {
+  h2_t sc;
+  __device__ __forceinline__ h2_t operator()(h2_t p) const { return p * sc; }
+};
+// int4: the 8 nibbles of w.  m0 / m1 = 0x000F000F / 0x00F000F0, mag = 0x64006400, s16 = 1 / 16, c0 = -(1024 + bias +
+// zp), c1 = -(64 + bias + zp): nibbles at bits 4-7 read 1024 + 16 q.  1 shift + 4 v_and_or + 2 v_pk_add_f16 + 2
+// v_pk_fma_f16; the callers choose where the constants live (literals, SGPRs, kernel arguments).
+template <class F = NoFold>
+__device__ __forceinline__ h8_t dq4_core(uint32_t w, uint32_t m0, uint32_t m1, uint32_t mag, h2_t s16, h2_t c0, h2_t c1,
+                                         F fold = F{}) {
+  const uint32_t w8 = w >> 8;
+  const h2_t p0 = fold(as_h2(and_or(w, m0, mag)) + c0);
+  const h2_t p1 = fold(__builtin_elementwise_fma(as_h2(and_or(w, m1, mag)), s16, c1));
+  const h2_t p2 = fold(as_h2(and_or(w8, m0, mag)) + c0);
+  const h2_t p3 = fold(__builtin_elementwise_fma(as_h2(and_or(w8, m1, mag)), s16, c1));
+  return pack_h8(p0, p1, p2, p3);
+}
+// int8: 8 bytes (two dwords); byte b becomes the fp16 1024 + b by a byte permute, c = -(1024 + 128 + zp)
+template <class F = NoFold>
+__device__ __forceinline__ h8_t dq8_core(uint32_t w0, uint32_t w1, h2_t c, F fold = F{}) {
+  const h2_t p0 = fold(as_h2(__builtin_amdgcn_perm(0x64646464u, w0, 0x04010400u)) + c);
+  const h2_t p1 = fold(as_h2(__builtin_amdgcn_perm(0x64646464u, w0, 0x04030402u)) + c);
+  const h2_t p2 = fold(as_h2(__builtin_amdgcn_perm(0x64646464u, w1, 0x04010400u)) + c);
+  const h2_t p3 = fold(as_h2(__builtin_amdgcn_perm(0x64646464u, w1, 0x04030402u)) + c);
+  return pack_h8(p0, p1, p2, p3);
+}
+
+// One MFMA step's B fragment (8 fp16 = exact integers q - zp) from the packed dwords, of the general kernels
+// (woq_kernels.hip, woq_gemv_kernel).  c2 = (-(1024 + bias + zp)) broadcast as half2.
+// The int8 and int2 arms are the twins of dq8_core and of gemm4's dq2 but extract all four pairs before the first add;
+// hipcc's schedule follows that order, and written pair by pair (through dq8_core) the 24 int8 woq_gemv_kernel and 23
+// kernels of woq_kernels.hip came out -6 .. +9 instructions different, so these copies stay.
 template <int BITS>
 __device__ __forceinline__ h8_t dequant_step(const u4_t& b, int d, h2_t c2) {
   h2_t p0, p1, p2, p3;
   if constexpr (BITS == 4) {
     uint32_t w = b[d];
-    p0 = as_h2(dq_and_or(w, 0x000F000Fu, 0x64006400u));
-    p1 = as_h2(dq_and_or(w >> 4, 0x000F000Fu, 0x64006400u));
-    p2 = as_h2(dq_and_or(w >> 8, 0x000F000Fu, 0x64006400u));
-    p3 = as_h2(dq_and_or(w >> 12, 0x000F000Fu, 0x64006400u));
+    p0 = as_h2(and_or(w, 0x000F000Fu, 0x64006400u));
+    p1 = as_h2(and_or(w >> 4, 0x000F000Fu, 0x64006400u));
+    p2 = as_h2(and_or(w >> 8, 0x000F000Fu, 0x64006400u));
+    p3 = as_h2(and_or(w >> 12, 0x000F000Fu, 0x64006400u));
   } else if constexpr (BITS == 2) {
     uint32_t w = b[d >> 1];
     int sh = (d & 1) * 8;
-    p0 = as_h2(dq_and_or(w >> (sh + 0), 0x00030003u, 0x64006400u));
-    p1 = as_h2(dq_and_or(w >> (sh + 2), 0x00030003u, 0x64006400u));
-    p2 = as_h2(dq_and_or(w >> (sh + 4), 0x00030003u, 0x64006400u));
-    p3 = as_h2(dq_and_or(w >> (sh + 6), 0x00030003u, 0x64006400u));
+    p0 = as_h2(and_or(w >> (sh + 0), 0x00030003u, 0x64006400u));
+    p1 = as_h2(and_or(w >> (sh + 2), 0x00030003u, 0x64006400u));
+    p2 = as_h2(and_or(w >> (sh + 4), 0x00030003u, 0x64006400u));
+    p3 = as_h2(and_or(w >> (sh + 6), 0x00030003u, 0x64006400u));
   } else {
     uint32_t w0 = b[2 * d], w1 = b[2 * d + 1];
     p0 = as_h2(__builtin_amdgcn_perm(0x64646464u, w0, 0x04010400u));
@@ -66,16 +128,7 @@ __device__ __forceinline__ h8_t dequant_step(const u4_t& b, int d, h2_t c2) {
   p1 += c2;
   p2 += c2;
   p3 += c2;
-  h8_t r;
-  r[0] = p0[0];
-  r[1] = p0[1];
-  r[2] = p1[0];
-  r[3] = p1[1];
-  r[4] = p2[0];
-  r[5] = p2[1];
-  r[6] = p3[0];
-  r[7] = p3[1];
-  return r;
+  return pack_h8(p0, p1, p2, p3);
 }
 
 // int2 through scaled magic numbers: crumb i of each 16-bit half (bits 2i .. 2i + 1 of x) or'ed into 0x6400 is the fp16
@@ -86,33 +139,18 @@ __device__ __forceinline__ h2_t zp_const(int bias_plus_zp);
 struct Dq2c {
   h2_t c0, c1, c2, c3;
 };
-__device__ __forceinline__ h2_t h2_splat(float v) {
-  h2_t r;
-  r[0] = _Float16(v);
-  r[1] = _Float16(v);
-  return r;
-}
 __device__ __forceinline__ Dq2c dq2_consts(int bias_plus_zp) {
   const float b = float(bias_plus_zp);
-  return Dq2c{h2_splat(-(1024.f + b)), h2_splat(-(256.f + b)), h2_splat(-(64.f + b)), h2_splat(-(16.f + b))};
+  return Dq2c{splat(-(1024.f + b)), splat(-(256.f + b)), splat(-(64.f + b)), splat(-(16.f + b))};
 }
 // x: the dword already shifted right by 8 for the odd step (b[d >> 1] >> ((d & 1) * 8))
 __device__ __forceinline__ h8_t dequant2s(uint32_t x, const Dq2c& c) {
   const uint32_t mag = 0x64006400u;
-  const h2_t p0 = as_h2(dq_and_or(x, 0x00030003u, mag)) + c.c0;
-  const h2_t p1 = __builtin_elementwise_fma(as_h2(dq_and_or(x, 0x000C000Cu, mag)), h2_splat(0.25f), c.c1);
-  const h2_t p2 = __builtin_elementwise_fma(as_h2(dq_and_or(x, 0x00300030u, mag)), h2_splat(0.0625f), c.c2);
-  const h2_t p3 = __builtin_elementwise_fma(as_h2(dq_and_or(x, 0x00C000C0u, mag)), h2_splat(0.015625f), c.c3);
-  h8_t r;
-  r[0] = p0[0];
-  r[1] = p0[1];
-  r[2] = p1[0];
-  r[3] = p1[1];
-  r[4] = p2[0];
-  r[5] = p2[1];
-  r[6] = p3[0];
-  r[7] = p3[1];
-  return r;
+  const h2_t p0 = as_h2(and_or(x, 0x00030003u, mag)) + c.c0;
+  const h2_t p1 = __builtin_elementwise_fma(as_h2(and_or(x, 0x000C000Cu, mag)), splat(0.25f), c.c1);
+  const h2_t p2 = __builtin_elementwise_fma(as_h2(and_or(x, 0x00300030u, mag)), splat(0.0625f), c.c2);
+  const h2_t p3 = __builtin_elementwise_fma(as_h2(and_or(x, 0x00C000C0u, mag)), splat(0.015625f), c.c3);
+  return pack_h8(p0, p1, p2, p3);
 }
 // one 32-deep step of an int2 tile (the dwords of a lane's 16 B) through the scaled magic numbers (measured faster than
 // dequant_step<2>, round 3)
@@ -177,16 +215,7 @@ __device__ __forceinline__ h8_t dequant_f4(const u4_t& b, int d, const F4Lut& L)
   const h2_t p23 = as_h2(__builtin_amdgcn_perm(hb, lb, 0x06020400u));
   const h2_t p45 = as_h2(__builtin_amdgcn_perm(ha, la, 0x07030501u));
   const h2_t p67 = as_h2(__builtin_amdgcn_perm(hb, lb, 0x07030501u));
-  h8_t r;
-  r[0] = p01[0];
-  r[1] = p01[1];
-  r[2] = p23[0];
-  r[3] = p23[1];
-  r[4] = p45[0];
-  r[5] = p45[1];
-  r[6] = p67[0];
-  r[7] = p67[1];
-  return r;
+  return pack_h8(p01, p23, p45, p67);
 }
 
 // NFloat 8-bit weights: raw codes in the int8 layout -> the exact fp16 of f8_to_fp32 (kernel_ref.h:984-1001, which
@@ -211,16 +240,7 @@ __device__ __forceinline__ h8_t dequant_f8(const u4_t& b, int d, bool e5m2) {
   const h2_t p1 = as_h2(f8_pair(w0, 0x04030402u, 0x03040204u, e5m2));
   const h2_t p2 = as_h2(f8_pair(w1, 0x04010400u, 0x01040004u, e5m2));
   const h2_t p3 = as_h2(f8_pair(w1, 0x04030402u, 0x03040204u, e5m2));
-  h8_t r;
-  r[0] = p0[0];
-  r[1] = p0[1];
-  r[2] = p1[0];
-  r[3] = p1[1];
-  r[4] = p2[0];
-  r[5] = p2[1];
-  r[6] = p3[0];
-  r[7] = p3[1];
-  return r;
+  return pack_h8(p0, p1, p2, p3);
 }
 
 template <int BITS>

@@ -25,44 +25,14 @@
 
 #include "woq_device.h"
 #include "woq_kernels.h"
+#include "woq_launch.h"
+#include "woq_pipe.h"
 
 namespace nad {
 namespace g2 {
 
 constexpr int BM = 256, BN = 128, KT = 128, ROWB = KT * 2;  // ROWB: bytes of one A row slice in LDS
 constexpr int ABUF = BM * ROWB;                              // one A buffer: 64 KiB
-
-__device__ __forceinline__ uint32_t and_or(uint32_t x, uint32_t m, uint32_t c) {
-  uint32_t r;
-  asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(r) : "v"(x), "s"(m), "v"(c));
-  return r;
-}
-
-__device__ __forceinline__ h2_t splat(float v) {
-  h2_t r;
-  r[0] = _Float16(v);
-  r[1] = _Float16(v);
-  return r;
-}
-
-__device__ __forceinline__ h8_t dequant4(uint32_t w, uint32_t m0, uint32_t m1, uint32_t mag, h2_t s16, h2_t c0,
-                                         h2_t c1) {
-  const uint32_t w8 = w >> 8;
-  const h2_t p0 = as_h2(and_or(w, m0, mag)) + c0;
-  const h2_t p1 = as_h2(and_or(w, m1, mag)) * s16 + c1;
-  const h2_t p2 = as_h2(and_or(w8, m0, mag)) + c0;
-  const h2_t p3 = as_h2(and_or(w8, m1, mag)) * s16 + c1;
-  h8_t r;
-  r[0] = p0[0];
-  r[1] = p0[1];
-  r[2] = p1[0];
-  r[3] = p1[1];
-  r[4] = p2[0];
-  r[5] = p2[1];
-  r[6] = p3[0];
-  r[7] = p3[1];
-  return r;
-}
 
 // LDS-DMA of one K step of A: 256 rows x 256 B = 64 one-KiB pieces, 8 per wave; lane l of piece p fills LDS chunk
 // (l & 15) of row 4p + (l >> 4) with source chunk (l & 15) ^ (row & 15).  Rows past M re-read row M-1 (their
@@ -134,13 +104,13 @@ __global__ __launch_bounds__(512, 1) void woq_gemm2_kernel(GemmArgs a, const _Fl
     return st == kScaleF32 ? __uint_as_float(x) : f16or;
   };
   // FOLD: this lane's two stripe scales of the current tile as fp16 pairs (fp16 scales: the stored bits, exact)
-  h2_t fsc[2] = {g2::splat(1.f), g2::splat(1.f)};
+  h2_t fsc[2] = {splat(1.f), splat(1.f)};
   auto scale_h2 = [&](uint32_t x) {
     if (st == kScaleF16) {
       const uint32_t h = (x >> ssh) & 0xFFFFu;
       return as_h2(h | (h << 16));
     }
-    return g2::splat(scale_f32(x));
+    return splat(scale_f32(x));
   };
 
   f4_t acc[4][4], accg[4][4];
@@ -192,9 +162,9 @@ __global__ __launch_bounds__(512, 1) void woq_gemm2_kernel(GemmArgs a, const _Fl
       for (int j = 0; j < 4; j++) {
         if constexpr (ASYM) {
           const float zf = float(z[j]);
-          bf[j] = dequant4(b[j][d], m0k, m1k, mag, s16, zc0 - splat(zf), zc1 - splat(zf));
+          bf[j] = dq4_core(b[j][d], m0k, m1k, mag, s16, zc0 - splat(zf), zc1 - splat(zf));
         } else {
-          bf[j] = dequant4(b[j][d], m0k, m1k, mag, s16, zc0, zc1);
+          bf[j] = dq4_core(b[j][d], m0k, m1k, mag, s16, zc0, zc1);
         }
       }
 #pragma unroll
@@ -315,58 +285,6 @@ constexpr int BBUF = BTILES + BSC + BZP;              // one K tile of B: 8 stri
 constexpr int NBR = 3;                                // B ring
 constexpr int LDS_BYTES = NA * HBUF + NBR * BBUF;     // 155 KiB
 
-__device__ __forceinline__ void glds16(const void* g, char* l) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)l, 16, 0, 0);
-}
-__device__ __forceinline__ void glds4(const void* g, char* l) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)l, 4, 0, 0);
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-// LDS reads in inline asm: hipcc puts a vmcnt(0) in front of every LDS read it can see while an LDS-DMA is in flight
-// (it cannot tell the buffers of one __shared__ array apart), which would drain the whole prefetch each half step.
-// Results are consumed only after an explicit lgkmcnt wait that names them (wait_lgk below).
-template <int OFF>
-__device__ __forceinline__ h8_t lds_b128(uint32_t addr) {
-  h8_t r;
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF));
-  return r;
-}
-template <int OFF>
-__device__ __forceinline__ uint2 lds_b64(uint32_t addr) {
-  uint2 r;
-  asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF));
-  return r;
-}
-template <int OFF>
-__device__ __forceinline__ uint32_t lds_b32(uint32_t addr) {
-  uint32_t r;
-  asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF));
-  return r;
-}
-template <size_t... I>
-__device__ __forceinline__ void lds_frags(h8_t (&f)[8], uint32_t addr, std::index_sequence<I...>) {
-  ((f[I] = lds_b128<int(I) * 16 * ROWB>(addr)), ...);
-}
-template <class T>
-__device__ __forceinline__ void tie(T& r) {
-  asm volatile("" : "+v"(r));
-}
-template <int N, class... T>
-__device__ __forceinline__ void wait_lgk(T&... regs) {
-  asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N));
-  (tie(regs), ...);  // each result is redefined after the wait: no use can be scheduled above it
-}
-__device__ __forceinline__ uint32_t lds_addr(const char* p) {
-  return uint32_t(reinterpret_cast<uintptr_t>((const __attribute__((address_space(3))) char*)p));
-}
-
 // FOLD: the group scale is multiplied into the fp16 B fragment (q * s rounded once to fp16, the host checked that every
 // q * s of the weight is an fp16 normal, DeviceWeight::fold_ok) and the MFMAs accumulate straight into the result: no
 // per-group fp32 accumulator, no group-end scaling (the reference itself dequantizes to bf16 for its AMX-BF16 core,
@@ -464,8 +382,8 @@ __global__ __launch_bounds__(512, 1) void woq_gemm3_kernel(GemmArgs a, const _Fl
   asm volatile("" ::: "memory");
 
   const uint32_t m0k = 0x000F000Fu, m1k = 0x00F000F0u, mag = 0x64006400u;
-  const h2_t s16 = g2::splat(1.f / 16.f);
-  const h2_t zc0 = g2::splat(-(1024.f + 8.f)), zc1 = g2::splat(-(64.f + 8.f));
+  const h2_t s16 = splat(1.f / 16.f);
+  const h2_t zc0 = splat(-(1024.f + 8.f)), zc1 = splat(-(64.f + 8.f));
   // fragment reads: A row wm*128 + i*16 + nl, chunk (dd*4 + kq) ^ f(row); B / scale / zp of stripe wn*2 + j
   uint32_t roff[2];
 #pragma unroll
@@ -484,13 +402,13 @@ __global__ __launch_bounds__(512, 1) void woq_gemm3_kernel(GemmArgs a, const _Fl
     return st == kScaleF32 ? __uint_as_float(x) : f16or;
   };
   // FOLD: this lane's two stripe scales of the current tile as fp16 pairs (fp16 scales: the stored bits, exact)
-  h2_t fsc[2] = {g2::splat(1.f), g2::splat(1.f)};
+  h2_t fsc[2] = {splat(1.f), splat(1.f)};
   auto scale_h2 = [&](uint32_t x) {
     if (st == kScaleF16) {
       const uint32_t h = (x >> ssh) & 0xFFFFu;
       return as_h2(h | (h << 16));
     }
-    return g2::splat(scale_f32(x));
+    return splat(scale_f32(x));
   };
 
   // hand-over: batch(u - 2) (the buffers half step u + 1 reads) has landed for this wave; batches u - 1 and u
@@ -537,8 +455,8 @@ __global__ __launch_bounds__(512, 1) void woq_gemm3_kernel(GemmArgs a, const _Fl
       fw1 = lds_b32<64>(bl + soff);
     }
     h8_t af0[8], af1[8];
-    lds_frags(af0, al + roff[0], std::make_index_sequence<8>{});
-    lds_frags(af1, al + roff[1], std::make_index_sequence<8>{});
+    read_frags<ROWB, 0>(af0, al + roff[0], std::make_index_sequence<8>{});
+    read_frags<ROWB, 0>(af1, al + roff[1], std::make_index_sequence<8>{});
     wait_lgk<8>(bv0, bv1, zw0, zw1, fw0, fw1, af0[0], af0[1], af0[2], af0[3], af0[4], af0[5], af0[6], af0[7]);
     if constexpr (FOLD && H == 0) {
       fsc[0] = scale_h2(fw0);
@@ -571,9 +489,9 @@ __global__ __launch_bounds__(512, 1) void woq_gemm3_kernel(GemmArgs a, const _Fl
       for (int j = 0; j < 2; j++) {
         if constexpr (ASYM) {
           const float zf = float(zp[j]);
-          bf[j] = g2::dequant4(bw[j][dd], m0k, m1k, mag, s16, zc0 - g2::splat(zf), zc1 - g2::splat(zf));
+          bf[j] = dq4_core(bw[j][dd], m0k, m1k, mag, s16, zc0 - splat(zf), zc1 - splat(zf));
         } else {
-          bf[j] = g2::dequant4(bw[j][dd], m0k, m1k, mag, s16, zc0, zc1);
+          bf[j] = dq4_core(bw[j][dd], m0k, m1k, mag, s16, zc0, zc1);
         }
         if constexpr (FOLD) {
           const h8_t s8 = {fsc[j][0], fsc[j][0], fsc[j][0], fsc[j][0], fsc[j][0], fsc[j][0], fsc[j][0], fsc[j][0]};
@@ -725,25 +643,15 @@ hipError_t launch_splitk_reduce(const GemmArgs& a, hipStream_t st) {
 hipError_t launch_gemm3(const GemmArgs& a, const _Float16* A16, int lda16, hipStream_t st) {
   const int nbm = (a.M + g3::BM - 1) / g3::BM, nbn = (a.w.ns + 7) / 8;
   const bool tpg1 = a.w.bs == g3::KT;
-  auto go = [&](auto k) -> hipError_t {
-    static bool attr[2][2][2] = {};  // opt in to 155 KiB of dynamic LDS once per instantiation
-    bool& done = attr[a.w.zps != nullptr][a.w.bs == g3::KT][a.fold ? 1 : 0];
-    if (!done) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         g3::LDS_BYTES);
-      if (e != hipSuccess) return e;
-      done = true;
-    }
-    hipLaunchKernelGGL(k, dim3(nbm * nbn * (a.ksplit > 1 ? a.ksplit : 1)), dim3(512), g3::LDS_BYTES, st, a, A16, lda16);
-    return hipGetLastError();
+  auto go = [&](auto asc, auto tc, auto fc) {
+    return launch_big_lds<g3::woq_gemm3_kernel<decltype(asc)::value, decltype(tc)::value, decltype(fc)::value>>(
+        dim3(nbm * nbn * (a.ksplit > 1 ? a.ksplit : 1)), dim3(512), g3::LDS_BYTES, st, a, A16, lda16);
   };
-  const bool asym = a.w.zps != nullptr;
-  if (a.fold) {
-    if (asym) return tpg1 ? go(g3::woq_gemm3_kernel<true, true, true>) : go(g3::woq_gemm3_kernel<true, false, true>);
-    return tpg1 ? go(g3::woq_gemm3_kernel<false, true, true>) : go(g3::woq_gemm3_kernel<false, false, true>);
-  }
-  if (asym) return tpg1 ? go(g3::woq_gemm3_kernel<true, true, false>) : go(g3::woq_gemm3_kernel<true, false, false>);
-  return tpg1 ? go(g3::woq_gemm3_kernel<false, true, false>) : go(g3::woq_gemm3_kernel<false, false, false>);
+  auto by_fold = [&](auto asc, auto tc) {
+    return a.fold ? go(asc, tc, std::true_type{}) : go(asc, tc, std::false_type{});
+  };
+  auto by_tpg = [&](auto asc) { return tpg1 ? by_fold(asc, std::true_type{}) : by_fold(asc, std::false_type{}); };
+  return a.w.zps != nullptr ? by_tpg(std::true_type{}) : by_tpg(std::false_type{});
 }
 
 hipError_t launch_cvt_act(const void* A, int act_t, int lda, int M, int K, int Kp, const int32_t* shuffle,
@@ -766,18 +674,12 @@ hipError_t launch_gemm2(const GemmArgs& a, const _Float16* A16, int lda16, hipSt
   const int nbm = (a.M + g2::BM - 1) / g2::BM, nbn = (a.w.ns + 7) / 8;
   const size_t lds = 2 * size_t(g2::ABUF);
   const bool tpg1 = a.w.bs == g2::KT;
-  auto go = [&](auto k) -> hipError_t {
-    static bool attr = false;  // per instantiation (distinct lambda argument types)
-    (void)attr;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       int(lds));
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k, dim3(nbm * nbn), dim3(512), lds, st, a, A16, lda16);
-    return hipGetLastError();
+  auto go = [&](auto asc, auto tc) {
+    return launch_big_lds<g2::woq_gemm2_kernel<decltype(asc)::value, decltype(tc)::value>>(dim3(nbm * nbn), dim3(512),
+                                                                                          lds, st, a, A16, lda16);
   };
-  const bool asym = a.w.zps != nullptr;
-  if (asym) return tpg1 ? go(g2::woq_gemm2_kernel<true, true>) : go(g2::woq_gemm2_kernel<true, false>);
-  return tpg1 ? go(g2::woq_gemm2_kernel<false, true>) : go(g2::woq_gemm2_kernel<false, false>);
+  auto by_tpg = [&](auto asc) { return tpg1 ? go(asc, std::true_type{}) : go(asc, std::false_type{}); };
+  return a.w.zps != nullptr ? by_tpg(std::true_type{}) : by_tpg(std::false_type{});
 }
 
 }  // namespace nad

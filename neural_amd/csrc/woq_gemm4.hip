@@ -24,6 +24,8 @@
 
 #include "woq_device.h"
 #include "woq_kernels.h"
+#include "woq_launch.h"
+#include "woq_pipe.h"
 
 namespace nad {
 namespace g4 {
@@ -62,37 +64,12 @@ constexpr int lds_bytes() {
   return NA * HBUF + nbr<BITS, G32, ASYM>() * bbuf<BITS, G32, ASYM>();
 }
 
-__device__ __forceinline__ uint32_t and_or(uint32_t x, uint32_t m, uint32_t c) {
-  uint32_t r;
-  asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(r) : "v"(x), "s"(m), "v"(c));
-  return r;
-}
-__device__ __forceinline__ h2_t splat(float v) {
-  h2_t r;
-  r[0] = _Float16(v);
-  r[1] = _Float16(v);
-  return r;
-}
-// int4: 8 nibbles of one dword -> 8 exact fp16 (q - 8 - zp), 0x6400 magic (as woq_gemm2.hip)
+// int4: dq4_core (woq_device.h) with literal masks and magic
 __device__ __forceinline__ h8_t dq4(uint32_t w, h2_t s16, h2_t c0, h2_t c1) {
-  const uint32_t m0 = 0x000F000Fu, m1 = 0x00F000F0u, mag = 0x64006400u;
-  const uint32_t w8 = w >> 8;
-  const h2_t p0 = as_h2(and_or(w, m0, mag)) + c0;
-  const h2_t p1 = as_h2(and_or(w, m1, mag)) * s16 + c1;
-  const h2_t p2 = as_h2(and_or(w8, m0, mag)) + c0;
-  const h2_t p3 = as_h2(and_or(w8, m1, mag)) * s16 + c1;
-  h8_t r;
-  r[0] = p0[0];
-  r[1] = p0[1];
-  r[2] = p1[0];
-  r[3] = p1[1];
-  r[4] = p2[0];
-  r[5] = p2[1];
-  r[6] = p3[0];
-  r[7] = p3[1];
-  return r;
+  return dq4_core(w, 0x000F000Fu, 0x00F000F0u, 0x64006400u, s16, c0, c1);
 }
-// int2: the 16-bit half `sh` (0 or 8) of a dword -> 8 exact fp16 (q - 2 - zp); field order of dequant_step<2>
+// int2: the 16-bit half `sh` (0 or 8) of a dword -> 8 exact fp16 (q - 2 - zp).  The twin of dequant_step<2>
+// (woq_device.h), which extracts all four pairs before the first add; see there why both stay.
 __device__ __forceinline__ h8_t dq2(uint32_t w, int sh, h2_t c) {
   const uint32_t m = 0x00030003u, mag = 0x64006400u;
   const uint32_t x = w >> sh;
@@ -100,97 +77,7 @@ __device__ __forceinline__ h8_t dq2(uint32_t w, int sh, h2_t c) {
   const h2_t p1 = as_h2(and_or(x >> 2, m, mag)) + c;
   const h2_t p2 = as_h2(and_or(x >> 4, m, mag)) + c;
   const h2_t p3 = as_h2(and_or(x >> 6, m, mag)) + c;
-  h8_t r;
-  r[0] = p0[0];
-  r[1] = p0[1];
-  r[2] = p1[0];
-  r[3] = p1[1];
-  r[4] = p2[0];
-  r[5] = p2[1];
-  r[6] = p3[0];
-  r[7] = p3[1];
-  return r;
-}
-
-// int8: 8 bytes (two dwords) -> 8 exact fp16 (q - 128 - zp): byte b becomes the fp16 1024 + b by a byte permute
-__device__ __forceinline__ h8_t dq8(uint32_t w0, uint32_t w1, h2_t c) {
-  const h2_t p0 = as_h2(__builtin_amdgcn_perm(0x64646464u, w0, 0x04010400u)) + c;
-  const h2_t p1 = as_h2(__builtin_amdgcn_perm(0x64646464u, w0, 0x04030402u)) + c;
-  const h2_t p2 = as_h2(__builtin_amdgcn_perm(0x64646464u, w1, 0x04010400u)) + c;
-  const h2_t p3 = as_h2(__builtin_amdgcn_perm(0x64646464u, w1, 0x04030402u)) + c;
-  h8_t r;
-  r[0] = p0[0];
-  r[1] = p0[1];
-  r[2] = p1[0];
-  r[3] = p1[1];
-  r[4] = p2[0];
-  r[5] = p2[1];
-  r[6] = p3[0];
-  r[7] = p3[1];
-  return r;
-}
-
-__device__ __forceinline__ void glds16(const void* g, char* l) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)l, 16, 0, 0);
-}
-__device__ __forceinline__ void glds4(const void* g, char* l) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)l, 4, 0, 0);
-}
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-// LDS reads in inline asm (hipcc would put a vmcnt(0) before every LDS read it can see while an LDS-DMA is in flight)
-template <int OFF>
-__device__ __forceinline__ h8_t lds_b128(uint32_t addr) {
-  h8_t r;
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF));
-  return r;
-}
-template <int OFF>
-__device__ __forceinline__ u4_t lds_u128(uint32_t addr) {
-  u4_t r;
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF));
-  return r;
-}
-template <int OFF>
-__device__ __forceinline__ uint2 lds_b64(uint32_t addr) {
-  uint2 r;
-  asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF));
-  return r;
-}
-template <int OFF>
-__device__ __forceinline__ uint32_t lds_b32(uint32_t addr) {
-  uint32_t r;
-  asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF));
-  return r;
-}
-__device__ __forceinline__ uint32_t lds_b32v(uint32_t addr) {  // runtime offset folded into the address
-  uint32_t r;
-  asm volatile("ds_read_b32 %0, %1" : "=v"(r) : "v"(addr));
-  return r;
-}
-template <size_t... I>
-__device__ __forceinline__ void lds_frags(h8_t (&f)[8], uint32_t addr, std::index_sequence<I...>) {
-  ((f[I] = lds_b128<int(I) * 16 * ROWB>(addr)), ...);
-}
-template <size_t... I>
-__device__ __forceinline__ void lds_frags16(h8_t (&f)[16], uint32_t addr, std::index_sequence<I...>) {
-  ((f[I] = lds_b128<int(I) * 16 * ROWB>(addr)), ...);
-}
-template <class T>
-__device__ __forceinline__ void tie(T& r) {
-  asm volatile("" : "+v"(r));
-}
-template <int N, class... T>
-__device__ __forceinline__ void wait_lgk(T&... regs) {
-  asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N));
-  (tie(regs), ...);
-}
-__device__ __forceinline__ uint32_t lds_addr(const char* p) {
-  return uint32_t(reinterpret_cast<uintptr_t>((const __attribute__((address_space(3))) char*)p));
+  return pack_h8(p0, p1, p2, p3);
 }
 
 // KSW (folded launches only): the waves split over K instead of M -- 1 (M) x 4 (N) x 2 (K), wave (wn, wk) owns a
@@ -416,7 +303,7 @@ __global__ __launch_bounds__(512, 1) void woq_gemm4_kernel(GemmArgs a, const _Fl
       const uint32_t sa = bl + soff + slot * 512;
       uint32_t s0 = lds_b32v(sa), s1 = lds_b32v(sa + 64);
       h8_t af[16];
-      lds_frags16(af, al + roffk, std::make_index_sequence<16>{});
+      read_frags<ROWB, 0>(af, al + roffk, std::make_index_sequence<16>{});
       wait_lgk<8>(b0, b1, e0, e1, z0, z1, s0, s1, af[0], af[1], af[2], af[3], af[4], af[5], af[6], af[7]);
       if constexpr (L) {
         wait_lgk<0>(af[8], af[9], af[10], af[11], af[12], af[13], af[14], af[15]);
@@ -431,7 +318,7 @@ __global__ __launch_bounds__(512, 1) void woq_gemm4_kernel(GemmArgs a, const _Fl
       for (int j = 0; j < 2; j++) {
         const float zf = ASYM ? float(int(int8_t((zw1[j] >> zsh) & 0xFFu))) : 0.f;
         if constexpr (BITS == 8)
-          bf[j] = dq8(bw8[j].x, bw8[j].y, zc0 - splat(zf));
+          bf[j] = dq8_core(bw8[j].x, bw8[j].y, zc0 - splat(zf));
         else if constexpr (BITS == 4)
           bf[j] = dq4(bw1[j], s16, zc0 - splat(zf), zc1 - splat(zf));
         else
@@ -499,8 +386,8 @@ __global__ __launch_bounds__(512, 1) void woq_gemm4_kernel(GemmArgs a, const _Fl
       sg[1][1] = lds_b32v(sa + 64);
     }
     h8_t af0[8], af1[8];
-    lds_frags(af0, al + roff[0], std::make_index_sequence<8>{});
-    lds_frags(af1, al + roff[1], std::make_index_sequence<8>{});
+    read_frags<ROWB, 0>(af0, al + roff[0], std::make_index_sequence<8>{});
+    read_frags<ROWB, 0>(af1, al + roff[1], std::make_index_sequence<8>{});
     wait_lgk<8>(b8[0], b8[1], bw[0][0], bw[0][1], bw[1][0], bw[1][1], zw[0][0], zw[0][1], zw[1][0], zw[1][1], sg[0][0], sg[0][1],
                 sg[1][0], sg[1][1], af0[0], af0[1], af0[2], af0[3], af0[4], af0[5], af0[6], af0[7]);
     const bool gstart = G32 || (u & (gh - 1)) == 0;
@@ -525,7 +412,7 @@ __global__ __launch_bounds__(512, 1) void woq_gemm4_kernel(GemmArgs a, const _Fl
       for (int j = 0; j < 2; j++) {
         const float zf = ASYM ? float(int(int8_t((zw[j][zi] >> zsh) & 0xFFu))) : 0.f;
         if constexpr (BITS == 8)
-          bf[j] = dq8(b8[j][2 * dd], b8[j][2 * dd + 1], zc0 - splat(zf));
+          bf[j] = dq8_core(b8[j][2 * dd], b8[j][2 * dd + 1], zc0 - splat(zf));
         else if constexpr (BITS == 4)
           bf[j] = dq4(bw[j][dd], s16, zc0 - splat(zf), zc1 - splat(zf));
         else
@@ -701,17 +588,12 @@ hipError_t launch_gemm4(const GemmArgs& a, int bits, const _Float16* A16, int ld
   // the stagger measured +4-14 % for int4 / int8 and neutral to -5 % for int2 (profiles/r02_gemm4_stagger.txt); with
   // the scale fold int2 gains too, +5-11 % (profiles/r03_gemm4_int2_stagger_fold.txt): off only for unfolded int2
   if (bits == 2 && !a.fold) ga.stagger = 0;
-  auto go = [&](auto k, int lds) -> hipError_t {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k, dim3(nbm * nbn * (a.ksplit > 1 ? a.ksplit : 1)), dim3(512), lds, st, ga, A16, lda16, gh_log2);
-    return hipGetLastError();
-  };
-#define NAD_G4(B, G, A) go(g4::woq_gemm4_kernel<B, G, A>, g4::lds_bytes<B, G, A>())
-#define NAD_G4F(B, G, A)                                                                              \
-  (a.ksw ? go(g4::woq_gemm4_kernel<B, G, A, true, true>, g4::lds_bytes<B, G, A>())                    \
-         : go(g4::woq_gemm4_kernel<B, G, A, true, false>, g4::lds_bytes<B, G, A>()))
+  const dim3 grid(nbm * nbn * (a.ksplit > 1 ? a.ksplit : 1));
+#define NAD_G4K(B, G, A, F, K)                                                                                   \
+  launch_big_lds<g4::woq_gemm4_kernel<B, G, A, F, K>>(grid, dim3(512), g4::lds_bytes<B, G, A>(), st, ga, A16, lda16, \
+                                                      gh_log2)
+#define NAD_G4(B, G, A) NAD_G4K(B, G, A, false, false)
+#define NAD_G4F(B, G, A) (a.ksw ? NAD_G4K(B, G, A, true, true) : NAD_G4K(B, G, A, true, false))
   if (bits == 4) {
     if (g32 && a.fold) return asym ? NAD_G4F(4, true, true) : NAD_G4F(4, true, false);
     if (g32) return asym ? NAD_G4(4, true, true) : NAD_G4(4, true, false);
@@ -726,6 +608,7 @@ hipError_t launch_gemm4(const GemmArgs& a, int bits, const _Float16* A16, int ld
   }
   if (a.fold) return asym ? NAD_G4F(2, false, true) : NAD_G4F(2, false, false);
   return asym ? NAD_G4(2, false, true) : NAD_G4(2, false, false);
+#undef NAD_G4K
 #undef NAD_G4
 #undef NAD_G4F
 }

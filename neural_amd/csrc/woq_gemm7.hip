@@ -22,6 +22,8 @@
 
 #include "woq_device.h"
 #include "woq_kernels.h"
+#include "woq_launch.h"
+#include "woq_pipe.h"
 
 namespace nad {
 namespace g7 {
@@ -67,107 +69,6 @@ struct Geo {
   static_assert(LDS <= 160 * 1024 && DA % 2 == 1, "geometry");
 };
 
-// LDS-DMA as raw buffer loads: 32-bit per-lane offsets fixed for the whole K loop, the moving part in an SGPR
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t brsrc(const void* p) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, -1, 0x00020000);
-}
-__device__ __forceinline__ void blds16(__amdgpu_buffer_rsrc_t r, uint32_t voff, uint32_t soff, char* l) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)l, 16, voff, soff, 0, 0);
-}
-__device__ __forceinline__ void blds4(__amdgpu_buffer_rsrc_t r, uint32_t voff, uint32_t soff, char* l) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)l, 4, voff, soff, 0, 0);
-}
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-// LDS reads in inline asm (hipcc would put vmcnt(0) in front of every LDS read it sees while an LDS-DMA is in flight);
-// results are consumed only after an explicit lgkmcnt wait that names them
-template <int OFF>
-__device__ __forceinline__ h8_t lds_b128(uint32_t addr) {
-  h8_t r;
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF));
-  return r;
-}
-template <int OFF>
-__device__ __forceinline__ uint2 lds_b64(uint32_t addr) {
-  uint2 r;
-  asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF));
-  return r;
-}
-template <int OFF>
-__device__ __forceinline__ uint32_t lds_b32(uint32_t addr) {
-  uint32_t r;
-  asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF));
-  return r;
-}
-template <class T>
-__device__ __forceinline__ void tie(T& r) {
-  asm volatile("" : "+v"(r));
-}
-template <int N, class... T>
-__device__ __forceinline__ void wait_lgk(T&... regs) {
-  asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N));
-  (tie(regs), ...);
-}
-template <int B, size_t... I>
-__device__ __forceinline__ void read_frags(h8_t* f, uint32_t addr, std::index_sequence<I...>) {
-  ((f[B + I] = lds_b128<int(B + I) * 16 * ROWB>(addr)), ...);
-}
-template <int B, size_t... I>
-__device__ __forceinline__ void tie_frags(h8_t* f, std::index_sequence<I...>) {
-  (tie(f[B + I]), ...);
-}
-__device__ __forceinline__ uint32_t lds_addr(const char* p) {
-  return uint32_t(reinterpret_cast<uintptr_t>((const __attribute__((address_space(3))) char*)p));
-}
-__device__ __forceinline__ uint32_t and_or(uint32_t x, uint32_t m, uint32_t c) {
-  uint32_t r;
-  asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(r) : "v"(x), "s"(m), "v"(c));
-  return r;
-}
-__device__ __forceinline__ h2_t splat(float v) {
-  h2_t r;
-  r[0] = _Float16(v);
-  r[1] = _Float16(v);
-  return r;
-}
-// one 32-deep step's B fragment: 8 nibbles -> fp16 (q - 8 - zp) * s, the product rounded once
-__device__ __forceinline__ h8_t dequant_fold(uint32_t w, uint32_t mag, h2_t s16, h2_t c0, h2_t c1, h2_t sc) {
-  const uint32_t w8 = w >> 8;
-  const h2_t p0 = (as_h2(and_or(w, 0x000F000Fu, mag)) + c0) * sc;
-  const h2_t p1 = __builtin_elementwise_fma(as_h2(and_or(w, 0x00F000F0u, mag)), s16, c1) * sc;
-  const h2_t p2 = (as_h2(and_or(w8, 0x000F000Fu, mag)) + c0) * sc;
-  const h2_t p3 = __builtin_elementwise_fma(as_h2(and_or(w8, 0x00F000F0u, mag)), s16, c1) * sc;
-  h8_t r;
-  r[0] = p0[0];
-  r[1] = p0[1];
-  r[2] = p1[0];
-  r[3] = p1[1];
-  r[4] = p2[0];
-  r[5] = p2[1];
-  r[6] = p3[0];
-  r[7] = p3[1];
-  return r;
-}
-
-// int8: a dword pair (8 bytes q + 128) -> fp16 (q - zp) * s: byte b becomes 1024 + b by a byte permute, c = -(1152 + zp)
-__device__ __forceinline__ h8_t dequant8_fold(uint32_t w0, uint32_t w1, h2_t c, h2_t sc) {
-  const h2_t p0 = (as_h2(__builtin_amdgcn_perm(0x64646464u, w0, 0x04010400u)) + c) * sc;
-  const h2_t p1 = (as_h2(__builtin_amdgcn_perm(0x64646464u, w0, 0x04030402u)) + c) * sc;
-  const h2_t p2 = (as_h2(__builtin_amdgcn_perm(0x64646464u, w1, 0x04010400u)) + c) * sc;
-  const h2_t p3 = (as_h2(__builtin_amdgcn_perm(0x64646464u, w1, 0x04030402u)) + c) * sc;
-  h8_t r;
-  r[0] = p0[0];
-  r[1] = p0[1];
-  r[2] = p1[0];
-  r[3] = p1[1];
-  r[4] = p2[0];
-  r[5] = p2[1];
-  r[6] = p3[0];
-  r[7] = p3[1];
-  return r;
-}
 // int2: one 32-deep step (the low 8 bits of each 16-bit half of x) -> fp16 (q - 2 - zp) * s: the exact integers of the
 // scaled magic numbers (dequant2s), then one rounding
 __device__ __forceinline__ h8_t dequant2_fold(uint32_t x, const Dq2c& q, h2_t sc) {
@@ -258,19 +159,16 @@ __global__ __launch_bounds__(512, 1) void woq_gemm7_kernel(GemmArgs a, const _Fl
     aoff[i] = uint32_t(grow) * uint32_t(lda16) * 2u + uint32_t(((lane & 7) ^ ((row >> 1) & 7)) * 16);
     adst[i] = smem + p * 1024;
   }
-  const auto ra = brsrc(reinterpret_cast<const char*>(A16) + size_t(kt0) * TK * 2);
-  const auto rb = brsrc(static_cast<const char*>(W.tiles) + size_t(kt0) * 1024);
-  const auto rnull = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(W.tiles), 0, 0, 0x00020000);
+  const auto ra = rsrc(reinterpret_cast<const char*>(A16) + size_t(kt0) * TK * 2, -1);
+  const auto rb = rsrc(static_cast<const char*>(W.tiles) + size_t(kt0) * 1024, -1);
+  const auto rnull = rsrc(W.tiles, 0);
   const uint32_t boffd = (uint32_t(min(bn * NS + wave, ns - 1)) * nt * 64 + lane) * 16;
   // scale / zero-point pieces: wave w copies 256-byte piece w % pieces of the tile's region; lane bytes past the tile's
   // share (a region rounded up to one piece) re-read its start into the unused tail
   constexpr int st = ST;
   // scales / zero points: a lane whose group lies past the last one (the zero-padded K tail of the last tile or half
   // step) gets an offset past the resource's end, which loads 0 without touching memory
-  constexpr uint32_t kOOB = 0x7FFF0000u;
-  const auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(W.scales), 0, int(kOOB), 0x00020000);
-  const auto rz = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(static_cast<const void*>(W.zps)), 0, int(kOOB),
-                                                    0x00020000);
+  const auto rs = rsrc(W.scales, kOOB), rz = rsrc(W.zps, kOOB);
   // first group of B buffer v of the K run (a tile, or a half step)
   auto group_of = [&](int v) -> uint32_t {
     const uint32_t x = HS ? uint32_t(kt0 * HPT + v) : uint32_t(kt0 + v);
@@ -398,11 +296,11 @@ __global__ __launch_bounds__(512, 1) void woq_gemm7_kernel(GemmArgs a, const _Fl
       }
     }
     const uint32_t al = lds_addr(smem + (u % NA) * HBUF) + roff;
-    read_frags<0>(af, al, std::make_index_sequence<HF>{});
+    read_frags<ROWB, 0>(af, al, std::make_index_sequence<HF>{});
   };
   auto read_hi = [&](int u) {
     const uint32_t al = lds_addr(smem + (u % NA) * HBUF) + roff;
-    read_frags<HF>(af, al, std::make_index_sequence<HF>{});
+    read_frags<ROWB, HF>(af, al, std::make_index_sequence<HF>{});
   };
   auto dequant = [&](auto Hc) {
     constexpr int H = decltype(Hc)::value;
@@ -426,12 +324,13 @@ __global__ __launch_bounds__(512, 1) void woq_gemm7_kernel(GemmArgs a, const _Fl
         }
       }
     }
+    // one 32-deep step's B fragments, (q - bias - zp) * s with the product rounded once
     if constexpr (BITS == 4) {
-      bf[0] = dequant_fold(bw0, mag, s16, c0[0], c1[0], sc[0]);
-      bf[1] = dequant_fold(bw1, mag, s16, c0[1], c1[1], sc[1]);
+      bf[0] = dq4_core(bw0, 0x000F000Fu, 0x00F000F0u, mag, s16, c0[0], c1[0], Fold{sc[0]});
+      bf[1] = dq4_core(bw1, 0x000F000Fu, 0x00F000F0u, mag, s16, c0[1], c1[1], Fold{sc[1]});
     } else if constexpr (BITS == 8) {
-      bf[0] = dequant8_fold(bw0, bx0, c0[0], sc[0]);
-      bf[1] = dequant8_fold(bw1, bx1, c0[1], sc[1]);
+      bf[0] = dq8_core(bw0, bx0, c0[0], Fold{sc[0]});
+      bf[1] = dq8_core(bw1, bx1, c0[1], Fold{sc[1]});
     } else {
       const uint32_t sh = uint32_t(wk) * 8u;
       bf[0] = dequant2_fold(bw0 >> sh, q2[0], sc[0]);
@@ -563,34 +462,22 @@ hipError_t G7_CAT(launch_gemm7_b, G7_BITS)(const GemmArgs& a, int bm, const _Flo
   constexpr int BITS = G7_BITS;
   const int nbm = (a.M + bm - 1) / bm, nbn = a.nwt > 1 ? a.nbn_all : (a.w.ns + g7::NS - 1) / g7::NS;
   const dim3 grid(nbm * nbn * (a.ksplit > 1 ? a.ksplit : 1));
-  auto go = [&](auto k, int lds, bool& done) -> hipError_t {
-    if (!done) {  // opt in to the dynamic LDS once per instantiation
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         lds);
-      if (e != hipSuccess) return e;
-      done = true;
-    }
-    hipLaunchKernelGGL(k, grid, dim3(512), lds, st, a, A16, lda16);
-    return hipGetLastError();
-  };
   // groups per B buffer: per tile (int4) or per half step (int2 / int8)
   const int gpt = BITS == 4 ? (a.w.bs == 32 ? 4 : (a.w.bs == 64 ? 2 : 1)) : (a.w.bs == 32 ? 2 : 1);
   auto pick = [&](auto bmc) -> hipError_t {
     constexpr int BMT = decltype(bmc)::value;
-    static bool attr[3][2][3] = {};
     const bool asym = a.w.zps != nullptr;
-    const int gi = gpt == 4 ? 2 : gpt - 1;
-    bool& d = attr[gi][asym][a.scale_t];
-    static bool attr_mw[2][3] = {};
     auto sel = [&](auto asc, auto stc, auto gc) {
       constexpr bool AS = decltype(asc)::value;
       constexpr int STT = decltype(stc)::value, GP = decltype(gc)::value;
       constexpr int LDS = g7::Geo<BMT, g7::Bbuf<BITS, GP, STT, AS>>::LDS;
       if constexpr (BITS == 4 && GP == 1 && BMT >= 64) {
-        if (a.nwt > 1) return go(g7::woq_gemm7_kernel<BITS, BMT, AS, STT, GP, true>, LDS, attr_mw[AS][a.scale_t]);
+        if (a.nwt > 1)
+          return launch_big_lds<g7::woq_gemm7_kernel<BITS, BMT, AS, STT, GP, true>>(grid, dim3(512), LDS, st, a, A16,
+                                                                                    lda16);
       }
       if (a.nwt > 1) return hipErrorInvalidValue;  // fused weights: int4 g128 * 2^j, 64-256-row tiles only
-      return go(g7::woq_gemm7_kernel<BITS, BMT, AS, STT, GP>, LDS, d);
+      return launch_big_lds<g7::woq_gemm7_kernel<BITS, BMT, AS, STT, GP>>(grid, dim3(512), LDS, st, a, A16, lda16);
     };
     auto by_gpt = [&](auto asc, auto stc) {
       if constexpr (BITS == 4) {

@@ -21,9 +21,11 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <utility>
 
 #include "woq_device.h"
 #include "woq_kernels.h"
+#include "woq_launch.h"
 
 namespace nad {
 namespace mid {
@@ -51,41 +53,8 @@ __device__ unsigned long long mid_trace_buf[kTraceSlots][kTraceMaxWg];
   } while (0)
 #endif
 
-constexpr int kOOB = 0x7FFF0000;  // a buffer offset past every resource: the load returns 0 and touches no memory
-constexpr int kAuxNT = 2;         // non-temporal: the weights are read once
+constexpr int kAuxNT = 2;  // non-temporal: the weights are read once
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const void* p, uint32_t bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, int(bytes), 0x00020000);
-}
-__device__ __forceinline__ uint32_t and_or(uint32_t x, uint32_t m, uint32_t c) {
-  uint32_t r;
-  asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(r) : "v"(x), "s"(m), "v"(c));
-  return r;
-}
-__device__ __forceinline__ h2_t splat(float v) {
-  h2_t r;
-  r[0] = _Float16(v);
-  r[1] = _Float16(v);
-  return r;
-}
-// int4: 8 nibbles -> exact fp16 (q - bias - zp) via the 0x6400 magic (woq_gemv.hip dequant4)
-__device__ __forceinline__ h8_t dq4(uint32_t w, uint32_t m0, uint32_t mag, h2_t s16, h2_t c0, h2_t c1) {
-  const uint32_t w8 = w >> 8, m1 = m0 << 4;
-  const h2_t p0 = as_h2(and_or(w, m0, mag)) + c0;
-  const h2_t p1 = __builtin_elementwise_fma(as_h2(and_or(w, m1, mag)), s16, c1);
-  const h2_t p2 = as_h2(and_or(w8, m0, mag)) + c0;
-  const h2_t p3 = __builtin_elementwise_fma(as_h2(and_or(w8, m1, mag)), s16, c1);
-  h8_t r;
-  r[0] = p0[0];
-  r[1] = p0[1];
-  r[2] = p1[0];
-  r[3] = p1[1];
-  r[4] = p2[0];
-  r[5] = p2[1];
-  r[6] = p3[0];
-  r[7] = p3[1];
-  return r;
-}
 // the group scales of a lane's 4 output columns: 4 fp32, or 4 fp16 / bf16 in two dwords (the 16-bit types share code,
 // selected per launch)
 template <bool F32>
@@ -235,9 +204,9 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW / 4,
         if constexpr (BITS == 4) {
           if constexpr (ASYM) {
             const float z = float(zp[j][s][g]);
-            bf = dq4(bw[j][s][d], m0, mag, s16, zc0 - splat(z), zc1 - splat(z));
+            bf = dq4_core(bw[j][s][d], m0, m0 << 4, mag, s16, zc0 - splat(z), zc1 - splat(z));
           } else {
-            bf = dq4(bw[j][s][d], m0, mag, s16, zc0, zc1);
+            bf = dq4_core(bw[j][s][d], m0, m0 << 4, mag, s16, zc0, zc1);
           }
         } else {
           bf = dequant2_step(bw[j][s], d, BIAS + zp[j][s][g]);
@@ -331,103 +300,73 @@ extern "C" int nad_mid_trace_fetch(void* host, size_t bytes, int clear) {
 
 int mid_lds_bytes(int rf, int s, int nw) { return nw * rf * s * 1024; }
 
-// BITS / GPT / ASYM / AT / RF / S / NW / SPW dispatch (mid_geometry: what the host plans with)
-template <int BITS, int GPT, bool ASYM, int AT, int RF, int S, int NW, int SPW>
-static hipError_t mid_go(const GemmArgs& a, int grid, hipStream_t st) {
-  const int lds = mid_lds_bytes(RF, S, NW);
-  const bool f32 = a.scale_t == kScaleF32;
-  auto k = f32 ? mid::woq_mid_kernel<BITS, GPT, ASYM, AT, RF, S, NW, SPW, true>
-               : mid::woq_mid_kernel<BITS, GPT, ASYM, AT, RF, S, NW, SPW, false>;
-  static bool attr[2] = {};  // opt in to > 64 KiB of dynamic LDS once per instantiation
-  if (!attr[f32] && lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       lds);
-    if (e != hipSuccess) return e;
-    attr[f32] = true;
-  }
-  hipLaunchKernelGGL(k, dim3(grid), dim3(NW * 64), lds, st, a);
-  return hipGetLastError();
-}
-
-// Geometry per format: 4 stripes per workgroup; int4 with one group per K tile or more: 8 waves x 1 stage (K tile)
-// each (round 6), except fp32 / bf16 rows at M > 48, whose raw rows, hi / lo fragments and 64 accumulators need more
-// than two waves' register budget: 4 waves (one per SIMD) x 2 stages; groups of half a tile: 8 x 1 to M = 32, then 4
-// waves x 1 (their scale / zero-point registers); groups of a quarter tile: 4 waves x 2 stages; int2 (256-deep tiles, 8 steps of activation fragments per stage)
-// 4 x 1.  Not taken: int2 at M > 32, int4 with 4 groups per tile (g32) at M > 32.
-void mid_geometry(int bits, int gpt, int act_t, int rf, int wide, int* s, int* nw, int* spw) {
-  *nw = 4;
+// The shape rule, once: S stripes per workgroup, NW waves, SPW stages (K tiles) per wave for a launch of rf row
+// fragments (M <= 16 rf); wide: 8-stripe workgroups where the rule has them.  s == 0: not taken (run_mid's gates).
+// mid_geometry() returns it to the host planner and mid_rf() instantiates exactly what it can return.
+struct MidShape {
+  int s, nw, spw;
+};
+constexpr MidShape mid_shape(int bits, int gpt, int act_t, int rf, int wide) {
+  if ((bits != 4 && bits != 2) || (gpt != 1 && gpt != 2 && gpt != 4) || rf < 1 || rf > 4) return {0, 0, 0};
+  // int2 (256-deep tiles, 8 steps of activation fragments per stage) and int4 with 4 groups per tile (g32): M <= 32
+  if ((bits == 2 || gpt == 4) && rf > 2) return {0, 0, 0};
   // 8 stripes x a 512-deep run: half the activation bytes per column.  Not at 3 / 4 row fragments: measured 1.1-1.3 us
   // SLOWER than 4 stripes at M = 33 .. 64, N = 4096 (no spills; the doubled slabs outweigh the halved activation bytes;
-  // profiles/r06_mid_wide_ab.txt)
-  if (wide && bits == 4 && rf <= 2 && gpt <= 2) {
-    *s = 8;
-    *spw = 1;
-    // 8 waves (measured N = 11008: fp16 M = 16 / 32 14.9 / 18.7 -> 13.1 / 15.6 us, fp32 15.7 / 21.6 -> 15.2 / 19.6;
-    // profiles/r06_mid_8waves_ab.txt), except g64 at 2 row fragments (its scale registers spill)
-    if (gpt == 1 || rf == 1) *nw = 8;
-    return;
-  }
-  *s = 4;
-  // int4 with one group per K tile or more: 8 waves x 1 stage -- the same 8-tile chunk as 4 waves x 2 stages, the
-  // loads and the dequant / MFMA of a chunk spread over two waves per SIMD (fp16 rows M = 12 / 32 / 64 7.71 / 9.44 /
-  // 12.62 -> 7.65 / 9.22 / 12.12 us; fp32 M = 48 15.2 -> 13.8; profiles/r06_mid_8waves_ab.txt); not for fp32 / bf16 rows
-  // at 4 row fragments (their hi / lo stage spills at two waves per SIMD: fp32 M = 64 19.2 -> 20.0 us)
+  // profiles/r06_mid_wide_ab.txt).  8 waves (measured N = 11008: fp16 M = 16 / 32 14.9 / 18.7 -> 13.1 / 15.6 us, fp32
+  // 15.7 / 21.6 -> 15.2 / 19.6; profiles/r06_mid_8waves_ab.txt), except g64 at 2 row fragments (its scale registers
+  // spill)
+  if (wide && bits == 4 && rf <= 2 && gpt <= 2) return {8, gpt == 1 || rf == 1 ? 8 : 4, 1};
+  // 4 stripes.  int4 with one group per K tile or more: 8 waves x 1 stage -- the same 8-tile chunk as 4 waves x 2
+  // stages, the loads and the dequant / MFMA of a chunk spread over two waves per SIMD (fp16 rows M = 12 / 32 / 64
+  // 7.71 / 9.44 / 12.62 -> 7.65 / 9.22 / 12.12 us; fp32 M = 48 15.2 -> 13.8; profiles/r06_mid_8waves_ab.txt); not for
+  // fp32 / bf16 rows at 4 row fragments (their raw rows, hi / lo fragments and 64 accumulators spill at two waves per
+  // SIMD: fp32 M = 64 19.2 -> 20.0 us)
+  if (bits == 4 && gpt == 1 && (rf <= 3 || act_t == kActF16)) return {4, 8, 1};
   // ... and int4 groups of half a tile (g64) at M <= 32 (M = 24 / 32: fp16 9.68 / 9.94 -> 9.29 / 9.64 us, fp32 12.09 /
   // 12.63 -> 11.23 / 11.73; profiles/r06_mid_8waves_ab.txt; beyond 2 row fragments their scale registers spill)
-  if (bits == 4 && gpt == 2 && rf <= 2) {
-    *nw = 8;
-    *spw = 1;
-    return;
-  }
-  if (bits == 4 && gpt == 1 && (rf <= 3 || act_t == kActF16)) {
-    *nw = 8;
-    *spw = 1;
-    return;
-  }
-  *spw = bits == 4 && (rf <= 2 || gpt == 1) ? 2 : 1;
+  if (bits == 4 && gpt == 2 && rf <= 2) return {4, 8, 1};
+  // else 4 waves (one per SIMD): x 2 stages for int4 at M <= 32 or one group per tile, x 1 for g64 at M > 32 (its
+  // scale / zero-point registers) and int2
+  return {4, 4, bits == 4 && (rf <= 2 || gpt == 1) ? 2 : 1};
 }
 
+void mid_geometry(int bits, int gpt, int act_t, int rf, int wide, int* s, int* nw, int* spw) {
+  const MidShape g = mid_shape(bits, gpt, act_t, rf, wide);
+  *s = g.s;
+  *nw = g.nw;
+  *spw = g.spw;
+}
+
+// One candidate of the dispatch: the shape of (RF, WIDE), launched if it is the one asked for.  The fp32 and 16-bit
+// scale forms are two kernels, each with its own opt-in to > 64 KiB of dynamic LDS.
+template <int BITS, int GPT, bool ASYM, int AT, int RF, int WIDE>
+static bool mid_try(const GemmArgs& a, int rf, int s, int grid, hipStream_t st, hipError_t* err) {
+  constexpr MidShape G = mid_shape(BITS, GPT, AT, RF, WIDE);
+  if constexpr (G.s != 0) {
+    if (rf != RF || s != G.s) return false;
+    constexpr int S = G.s, NW = G.nw, SPW = G.spw;
+    const dim3 g(grid), b(NW * 64);
+    const size_t lds = mid_lds_bytes(RF, S, NW);
+    *err = a.scale_t == kScaleF32
+               ? launch_big_lds<mid::woq_mid_kernel<BITS, GPT, ASYM, AT, RF, S, NW, SPW, true>>(g, b, lds, st, a)
+               : launch_big_lds<mid::woq_mid_kernel<BITS, GPT, ASYM, AT, RF, S, NW, SPW, false>>(g, b, lds, st, a);
+    return true;
+  }
+  return false;
+}
+
+// every (rf, wide) = (I / 2 + 1, I % 2) of this format and activation type: the kernels compiled are the shapes
+// mid_shape returns, no others.  Where wide does not change the shape (rf 3 / 4, gpt 4, int2) the pair is one kernel
+// and one launch_big_lds flag; the first of the two always matches, the second is never reached.
+template <int BITS, int GPT, bool ASYM, int AT, size_t... I>
+static hipError_t mid_rf(const GemmArgs& a, int rf, int s, int grid, hipStream_t st, std::index_sequence<I...>) {
+  hipError_t err = hipErrorInvalidValue;
+  (void)(mid_try<BITS, GPT, ASYM, AT, int(I / 2) + 1, int(I % 2)>(a, rf, s, grid, st, &err) || ...);
+  return err;
+}
 template <int BITS, int GPT, bool ASYM, int AT>
 static hipError_t mid_rf(const GemmArgs& a, int rf, int s, int grid, hipStream_t st) {
-  if constexpr (BITS == 4) {
-    constexpr int SPW3 = GPT == 1 ? 2 : 1;  // M > 32
-    if constexpr (GPT <= 2) {
-      if (s == 8 && rf == 1) return mid_go<BITS, GPT, ASYM, AT, 1, 8, 8, 1>(a, grid, st);
-      if (s == 8 && rf == 2) {
-        if constexpr (GPT == 1) return mid_go<BITS, GPT, ASYM, AT, 2, 8, 8, 1>(a, grid, st);
-        return mid_go<BITS, GPT, ASYM, AT, 2, 8, 4, 1>(a, grid, st);
-      }
-    }
-    if (s != 4) return hipErrorInvalidValue;
-    if constexpr (GPT <= 2) {  // 8 waves x 1 stage (mid_geometry)
-      if (rf == 1) return mid_go<BITS, GPT, ASYM, AT, 1, 4, 8, 1>(a, grid, st);
-      if (rf == 2) return mid_go<BITS, GPT, ASYM, AT, 2, 4, 8, 1>(a, grid, st);
-    }
-    if constexpr (GPT == 1) {
-      if (rf == 3) return mid_go<BITS, GPT, ASYM, AT, 3, 4, 8, 1>(a, grid, st);
-      if constexpr (AT == kActF16) {  // fp32 / bf16 rows at 4 row fragments: 4 waves (their hi / lo stage spills)
-        if (rf == 4) return mid_go<BITS, GPT, ASYM, AT, 4, 4, 8, 1>(a, grid, st);
-      }
-    }
-    switch (rf) {
-      case 1:
-        return mid_go<BITS, GPT, ASYM, AT, 1, 4, 4, 2>(a, grid, st);
-      case 2:
-        return mid_go<BITS, GPT, ASYM, AT, 2, 4, 4, 2>(a, grid, st);
-      default:
-        if constexpr (GPT == 4) {
-          return hipErrorInvalidValue;  // g32 at M > 32: not taken (run_mid)
-        } else {
-          return rf == 3 ? mid_go<BITS, GPT, ASYM, AT, 3, 4, 4, SPW3>(a, grid, st)
-                         : mid_go<BITS, GPT, ASYM, AT, 4, 4, 4, SPW3>(a, grid, st);
-        }
-    }
-  } else {
-    // int2 (8 steps of activation fragments per 256-deep stage): M <= 32 only (run_mid)
-    if (s != 4) return hipErrorInvalidValue;
-    return rf == 1 ? mid_go<BITS, GPT, ASYM, AT, 1, 4, 4, 1>(a, grid, st)
-                   : mid_go<BITS, GPT, ASYM, AT, 2, 4, 4, 1>(a, grid, st);
-  }
+  return mid_rf<BITS, GPT, ASYM, AT>(a, rf, s, grid, st, std::make_index_sequence<8>{});
 }
 
 template <int BITS, int GPT, bool ASYM>

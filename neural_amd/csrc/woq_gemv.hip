@@ -39,6 +39,7 @@
 
 #include "woq_device.h"
 #include "woq_kernels.h"
+#include "woq_launch.h"
 
 namespace nad {
 
@@ -66,8 +67,6 @@ __device__ unsigned long long nad_trace_buf[kTraceSlots][kTraceMaxWg];
   } while (0)
 #endif
 
-constexpr int kOOB = 0x7FFF0000;  // a buffer offset past every resource: the load returns 0 and touches no memory
-
 // virtual stripe -> (weight index, stripe within that weight); all wave-uniform
 __device__ __forceinline__ void vstripe(const GemvArgs& a, int v, int& w, int& s) {
   if (a.dual) {
@@ -82,10 +81,6 @@ __device__ __forceinline__ void vstripe(const GemvArgs& a, int v, int& w, int& s
 template <class T>
 __device__ __forceinline__ T sel3(int w, T x0, T x1, T x2) {
   return w == 0 ? x0 : (w == 1 ? x1 : x2);
-}
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const void* p, int bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, bytes, 0x00020000);
 }
 
 // ------------------------------------------------------------------------------------------------ weight stream
@@ -191,36 +186,8 @@ struct Dq4 {
   h2_t c0, c1;           // -(1024 + bias) and -(64 + bias): the symmetric weights' zero point folded into the magic's
 };
 
-// (x & m) | c in one VOP3 instruction (hipcc splits it when both constants sit in SGPRs: one constant-bus read on gfx9)
-__device__ __forceinline__ uint32_t and_or(uint32_t x, uint32_t m, uint32_t c) {
-  uint32_t r;
-  asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(r) : "v"(x), "s"(m), "v"(c));
-  return r;
-}
-
 __device__ __forceinline__ h8_t dequant4(uint32_t w, const Dq4& q, h2_t c0, h2_t c1) {
-  const uint32_t w8 = w >> 8;
-  const h2_t p0 = as_h2(and_or(w, q.m0, q.mag)) + c0;
-  const h2_t p1 = as_h2(and_or(w, q.m1, q.mag)) * q.s16 + c1;
-  const h2_t p2 = as_h2(and_or(w8, q.m0, q.mag)) + c0;
-  const h2_t p3 = as_h2(and_or(w8, q.m1, q.mag)) * q.s16 + c1;
-  h8_t r;
-  r[0] = p0[0];
-  r[1] = p0[1];
-  r[2] = p1[0];
-  r[3] = p1[1];
-  r[4] = p2[0];
-  r[5] = p2[1];
-  r[6] = p3[0];
-  r[7] = p3[1];
-  return r;
-}
-
-__device__ __forceinline__ h2_t splat(float v) {
-  h2_t r;
-  r[0] = _Float16(v);
-  r[1] = _Float16(v);
-  return r;
+  return dq4_core(w, q.m0, q.m1, q.mag, q.s16, c0, c1);
 }
 
 // a group scale from the dword load_stage fetched: f32 as is, 16-bit types from the half selected by `sh`
@@ -1135,21 +1102,6 @@ __global__ __launch_bounds__((m1_max_threads<GPT, KSN>())) void woq_gemv_m1s_ker
 }
 
 // ------------------------------------------------------------------------------------------------ launcher
-// Opt kernel K in to > 64 KiB of dynamic LDS once (the flag is K's own: one instance of this template per kernel
-// instantiation), then launch it.
-template <auto K, class... Args>
-static hipError_t launch_big_lds(dim3 g, dim3 b, size_t lds, hipStream_t st, const Args&... args) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       160 * 1024);
-    if (e != hipSuccess) return e;
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(K, g, b, lds, st, args...);
-  return hipGetLastError();
-}
-
 // the most (stripe, K-slice) stages any wave of a single-problem launch streams
 static int m1_stages_per_wave(const GemvArgs& a, int ksn, int waves) {
   const int nsl = (a.nt + ksn - 1) / ksn;

@@ -18,6 +18,7 @@
 
 #include "woq_device.h"
 #include "woq_kernels.h"
+#include "woq_launch.h"
 #include "woq_layout.h"
 
 namespace nad {
@@ -116,8 +117,8 @@ hipError_t launch_q6k_unpack(const DeviceWeight& w, float* out, hipStream_t st) 
 // The fp16 pair (q_j, q_j+1) of pair i of a group: lo already shifted right by 4 i, hi shifted so that its crumb pair
 // sits at bits 4..5 / 20..21 (q6k_hi_at4)
 __device__ __forceinline__ h2_t q6k_pair(uint32_t lo_sh, uint32_t hi_at4, h2_t m1056) {
-  const uint32_t t = dq_and_or(lo_sh, 0x000F000Fu, 0x64006400u);
-  return as_h2(dq_and_or(hi_at4, 0x00300030u, t)) + m1056;
+  const uint32_t t = and_or(lo_sh, 0x000F000Fu, 0x64006400u);
+  return as_h2(and_or(hi_at4, 0x00300030u, t)) + m1056;
 }
 // the crumb pair at position i (bits 2 i, 2 i + 16) of hi moved to bits 4 / 20
 template <int I>
@@ -218,7 +219,7 @@ __global__ __launch_bounds__(kQ6kWaves * 64) void woq_q6k_gemv_kernel(Q6kGemvArg
   }
   __syncthreads();
 
-  const h2_t m1056 = h2_splat(-1056.f);
+  const h2_t m1056 = splat(-1056.f);
   const f4_t zero4{0.f, 0.f, 0.f, 0.f};
   // this lane's A fragments: row nl of LDS, four fp16 at k = 256 b + 16 g + 4 kq.  A lane past the staged rows reads
   // row 0 instead (in bounds, finite): its row of the product is one nobody reads
@@ -315,26 +316,13 @@ bool q6k_gemv_geometry(int m, int k, int ns, int act_t, int cus, Q6kGemvGeom* g)
   return true;
 }
 
-template <auto K, class Args>
-static hipError_t q6k_launch_lds(dim3 g, dim3 b, size_t lds, hipStream_t st, const Args& args) {
-  static bool attr_set = false;  // opt the kernel in to > 64 KiB of dynamic LDS once
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       int(kQ6kLdsMax));
-    if (e != hipSuccess) return e;
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(K, g, b, lds, st, args);
-  return hipGetLastError();
-}
-
 hipError_t launch_q6k_gemv(const GemmArgs& a, int act_t, const Q6kGemvGeom& g, hipStream_t st) {
   if (a.M < 1 || a.M > 16 || a.K % 256 != 0 || g.lds > kQ6kLdsMax || g.rows_pp < 1) return hipErrorInvalidValue;
   Q6kGemvArgs qa{a, g.rows_pp};
   const dim3 grid(g.grid, g.passes), block(kQ6kWaves * 64);
-  if (act_t == kActF32) return q6k_launch_lds<woq_q6k_gemv_kernel<kActF32>>(grid, block, g.lds, st, qa);
-  if (act_t == kActF16) return q6k_launch_lds<woq_q6k_gemv_kernel<kActF16>>(grid, block, g.lds, st, qa);
-  return q6k_launch_lds<woq_q6k_gemv_kernel<kActBF16>>(grid, block, g.lds, st, qa);
+  if (act_t == kActF32) return launch_big_lds<woq_q6k_gemv_kernel<kActF32>>(grid, block, g.lds, st, qa);
+  if (act_t == kActF16) return launch_big_lds<woq_q6k_gemv_kernel<kActF16>>(grid, block, g.lds, st, qa);
+  return launch_big_lds<woq_q6k_gemv_kernel<kActBF16>>(grid, block, g.lds, st, qa);
 }
 
 // ------------------------------------------------------------------------------------------------ GEMM, M > 16
@@ -370,7 +358,7 @@ __global__ __launch_bounds__(512) void woq_q6k_gemm_kernel(GemmArgs a) {
   const u4_t* qp = static_cast<const u4_t*>(W.tiles);
   const u4_t* scp = reinterpret_cast<const u4_t*>(W.zps);
   const _Float16* dp = static_cast<const _Float16*>(W.scales);
-  const h2_t m1056 = h2_splat(-1056.f);
+  const h2_t m1056 = splat(-1056.f);
 
   size_t sbi[4];  // (stripe, superblock 0) index of the wave's stripes, clamped to the last stripe
 #pragma unroll
@@ -419,7 +407,7 @@ __global__ __launch_bounds__(512) void woq_q6k_gemm_kernel(GemmArgs a) {
         const uint32_t lw = lo[j][dd];
         const uint32_t hw = (half ? (dd < 2 ? hi[j][2] : hi[j][3]) : (dd < 2 ? hi[j][0] : hi[j][1])) >> (8 * (dd & 1));
         const int g0 = 8 * half + 2 * dd;
-        const h2_t s0h = h2_splat(float(q6k_sc(sc[j], g0))), s1h = h2_splat(float(q6k_sc(sc[j], g0 + 1)));
+        const h2_t s0h = splat(float(q6k_sc(sc[j], g0))), s1h = splat(float(q6k_sc(sc[j], g0 + 1)));
         const h2_t p0 = q6k_pair(lw, q6k_hi_at4<0>(hw), m1056) * s0h;
         const h2_t p1 = q6k_pair(lw >> 4, q6k_hi_at4<1>(hw), m1056) * s0h;
         const h2_t p2 = q6k_pair(lw >> 8, q6k_hi_at4<2>(hw), m1056) * s1h;
@@ -670,9 +658,9 @@ __device__ __forceinline__ uint32_t q6k_bytes(const u4_t& lo0, const u4_t& lo1, 
   constexpr int GP = G & 1, G4 = G & 3;
   const uint32_t x = GP ? lo >> 8 : lo;
   uint32_t t = x & 0x000F000Fu;
-  t = dq_and_or(x << 4, 0x0F000F00u, t);
-  t = dq_and_or(q6k_shl<4 - 4 * G4>(hw), 0x00300030u, t);
-  return dq_and_or(q6k_shl<10 - 4 * G4>(hw), 0x30003000u, t);
+  t = and_or(x << 4, 0x0F000F00u, t);
+  t = and_or(q6k_shl<4 - 4 * G4>(hw), 0x00300030u, t);
+  return and_or(q6k_shl<10 - 4 * G4>(hw), 0x30003000u, t);
 }
 
 // RS: the row sets of four rows a pass works on (1: the decode case; 2; 4) = Q6kI8Geom::rs_pp.  All RS of them are
@@ -877,18 +865,18 @@ hipError_t launch_q6k_i8(const GemmArgs& a, int act_t, const Q6kI8Geom& g, hipSt
   const dim3 grid(g.grid, g.passes), block(kQ6kWaves * 64);
   if (g.rs_pp != (g.rows_pp <= 4 ? 1 : (g.rows_pp <= 8 ? 2 : 4))) return hipErrorInvalidValue;
   if (g.rs_pp == 1) {
-    if (act_t == kActF32) return q6k_launch_lds<woq_q6k_i8_kernel<kActF32, 1>>(grid, block, g.lds, st, qa);
-    if (act_t == kActF16) return q6k_launch_lds<woq_q6k_i8_kernel<kActF16, 1>>(grid, block, g.lds, st, qa);
-    return q6k_launch_lds<woq_q6k_i8_kernel<kActBF16, 1>>(grid, block, g.lds, st, qa);
+    if (act_t == kActF32) return launch_big_lds<woq_q6k_i8_kernel<kActF32, 1>>(grid, block, g.lds, st, qa);
+    if (act_t == kActF16) return launch_big_lds<woq_q6k_i8_kernel<kActF16, 1>>(grid, block, g.lds, st, qa);
+    return launch_big_lds<woq_q6k_i8_kernel<kActBF16, 1>>(grid, block, g.lds, st, qa);
   }
   if (g.rs_pp == 2) {
-    if (act_t == kActF32) return q6k_launch_lds<woq_q6k_i8_kernel<kActF32, 2>>(grid, block, g.lds, st, qa);
-    if (act_t == kActF16) return q6k_launch_lds<woq_q6k_i8_kernel<kActF16, 2>>(grid, block, g.lds, st, qa);
-    return q6k_launch_lds<woq_q6k_i8_kernel<kActBF16, 2>>(grid, block, g.lds, st, qa);
+    if (act_t == kActF32) return launch_big_lds<woq_q6k_i8_kernel<kActF32, 2>>(grid, block, g.lds, st, qa);
+    if (act_t == kActF16) return launch_big_lds<woq_q6k_i8_kernel<kActF16, 2>>(grid, block, g.lds, st, qa);
+    return launch_big_lds<woq_q6k_i8_kernel<kActBF16, 2>>(grid, block, g.lds, st, qa);
   }
-  if (act_t == kActF32) return q6k_launch_lds<woq_q6k_i8_kernel<kActF32, 4>>(grid, block, g.lds, st, qa);
-  if (act_t == kActF16) return q6k_launch_lds<woq_q6k_i8_kernel<kActF16, 4>>(grid, block, g.lds, st, qa);
-  return q6k_launch_lds<woq_q6k_i8_kernel<kActBF16, 4>>(grid, block, g.lds, st, qa);
+  if (act_t == kActF32) return launch_big_lds<woq_q6k_i8_kernel<kActF32, 4>>(grid, block, g.lds, st, qa);
+  if (act_t == kActF16) return launch_big_lds<woq_q6k_i8_kernel<kActF16, 4>>(grid, block, g.lds, st, qa);
+  return launch_big_lds<woq_q6k_i8_kernel<kActBF16, 4>>(grid, block, g.lds, st, qa);
 }
 
 }  // namespace nad

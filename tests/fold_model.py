@@ -4,9 +4,9 @@ gemm7 folds the group scale into its fp16 B operand.  As read from woq_gemm7.hip
 
   * scale_h2 turns the stored scale into fp16 once: an fp16 scale is used bit for bit, an fp32 or bf16 one goes through
     `_Float16(float)`, round to nearest even (a bf16's 8 significant bits always fit, so only fp32 scales round here);
-  * dequant_fold / dequant8_fold / dequant2_fold build the integer q - zp exactly in fp16 -- magic-number mantissa
-    tricks whose additions, and the fused multiply-adds by 1/16, 1/4 ..., all stay on integers below 2048 -- and
-    multiply it once by that fp16 scale with a packed fp16 multiply: one rounding to nearest even.
+  * dq4_core / dq8_core with Fold (woq_device.h) and dequant2_fold build the integer q - zp exactly in fp16 --
+    magic-number mantissa tricks whose additions, and the fused multiply-adds by 1/16, 1/4 ..., all stay on integers
+    below 2048 -- and multiply it once by that fp16 scale with a packed fp16 multiply: one rounding to nearest even.
 
 So w16 = fp16(fp32(q - zp) * fp32(fp16(s))): the fp32 product of an integer of at most 9 bits and an 11-bit significand
 is exact, and its conversion to fp16 is the one rounding of the kernel's multiply.  Every |q - zp| >= 1 times a scale in

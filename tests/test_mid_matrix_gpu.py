@@ -1,6 +1,6 @@
 """Every reachable woq_mid_kernel instantiation against the exact hi / lo model (tests/mid_model.py).
 
-launch_gemm_mid -> mid_at -> mid_rf -> mid_go resolves a launch over bits x groups per K tile x sym / asym x activation
+launch_gemm_mid -> mid_at -> mid_rf -> mid_try resolves a launch over bits x groups per K tile x sym / asym x activation
 type x (row fragments RF, stripes S, waves NW, stages SPW) x fp32 / 16-bit scales (bf16 or fp16 at run time).  Here
 each reachable one is run by name -- M sets RF, NAD_MID_WIDE the stripes, and the plan's threads (NW x 64) and grid
 (stripe groups x K runs) prove which one ran -- on weights whose codes, scales and zero points span their whole ranges
@@ -24,13 +24,8 @@ The 60 reachable (bits, gpt, activation type, RF, S, NW, SPW), from mid_geometry
 
 times sym / asym and fp32 / 16-bit scales: 240 kernels, 360 launches with bf16 and fp16 scales apart.
 
-Compiled by mid_rf but reached by no launch (mid_geometry never asks for them), for a later cleanup -- 16 tuples, 64
-kernels with sym / asym and the two scale forms:
-
-  * int4 gpt 1 and gpt 2, RF 1 / 2, (4, 4, 2), every activation type (12): the 8-wave forms return first, so cases 1
-    and 2 of mid_rf's `switch (rf)` are live for gpt 4 only;
-  * int4 gpt 1, RF 3, (4, 4, 2), every activation type (3): RF 3 returns at 8 waves before the switch's default;
-  * int4 gpt 1, RF 4, (4, 4, 2), fp16 rows (1): they return at 8 waves; only fp32 / bf16 rows reach the default.
+The compiled set equals this reachable set: mid_rf instantiates the shapes mid_geometry's rule (mid_shape) can return
+and no others, and tests/test_mid_instances_cpu.py holds the built library's woq_mid_kernel symbols to these 240.
 
 Each launch prints one line; profiles/mid_matrix_errors.txt keeps them.
 """
@@ -63,8 +58,9 @@ VARIANTS = {"one": 1, "runs": 3}        # NAD_MID_KS
 # one group size per (bits, groups per K tile)
 FORMATS = [(S4, 32), (S4, 64), (S4, 128), (S2, 64), (S2, 128), (S2, 256)]
 
-# Transcribed from mid_geometry and mid_rf (woq_gemm_mid.hip) and run_mid's M gates -- not computed by the library: a
-# change to the geometry is a conscious edit here.  (bits, gpt, activation types, NAD_MID_WIDE, RFs, S, NW, SPW)
+# Transcribed from mid_shape (woq_gemm_mid.hip: mid_geometry and mid_rf both come from it) and run_mid's M gates -- not
+# computed by the library: a change to the geometry is a conscious edit here.
+# (bits, gpt, activation types, NAD_MID_WIDE, RFs, S, NW, SPW)
 GEOMETRY = [
     (4, 1, ACTS,             0, (1, 2, 3), 4, 8, 1),
     (4, 1, ("fp16",),        0, (4,),      4, 8, 1),

@@ -117,3 +117,17 @@ def test_mid_geometry_table_matches_the_plan(knob):
             for act in ACTS:
                 assert bestla.plan_forward(bits, N, k, bs, "fp16", True, M_OF_RF[3], act)["kernel"] != "woq_mid_kernel"
     assert len(seen) == 60 and sum(len(row[2]) * len(row[4]) for row in GEOMETRY) == 60
+
+
+def test_more_than_four_row_fragments_are_declined(knob):
+    """NAD_MID_MAX_M above 64 does not stretch the kernel: it has shapes for 4 row fragments (M <= 64), so the host's
+    dry run sends M = 65 and 80 to another kernel, and M = 64 still to this one."""
+    from neural_amd import bestla
+    knob("NAD_MID_MAX_M", 80)
+    for qt, bs in [(fm.S4, 128), (fm.S4, 64)]:
+        k = variant_k(qt)
+        for act in ACTS:
+            for asym in (False, True):
+                assert bestla.plan_forward(4, N, k, bs, "fp16", asym, 64, act)["kernel"] == "woq_mid_kernel"
+                for m in (65, 80):
+                    assert bestla.plan_forward(4, N, k, bs, "fp16", asym, m, act)["kernel"] != "woq_mid_kernel", (bs, m)
