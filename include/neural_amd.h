@@ -192,6 +192,8 @@ int nad_device_forward(const void* act, int act_dtype, const void* devstor, floa
 #define NAD_KERNEL_Q6K_GEMV 11 /* woq_q6k_gemv_kernel: GGUF Q6_K, M <= 16 (sub-scales in fp32: flags bit 0 clear) */
 #define NAD_KERNEL_Q6K_GEMM 12 /* woq_q6k_gemm_kernel: GGUF Q6_K, M > 16 (sc * q folded into fp16: flags bit 0 set) */
 #define NAD_KERNEL_Q6K_I8 13   /* woq_q6k_i8_kernel: GGUF Q6_K in mode NAD_COMPUTE_Q8_K, any M (flags bit 0 clear) */
+#define NAD_KERNEL_GEMV_ROUTED 14 /* woq_gemv_m1_routed_kernel: expert matmuls routed on the device (nad_plan_moe) */
+#define NAD_KERNEL_MOE_COMBINE 15 /* moe_combine_kernel: the weighted sum of the slot results (nad_plan_moe) */
 int nad_plan_forward(int bits, int n, int k, int blocksize, int scale_t, int asym, int m, int act_dtype, int64_t* out,
                      int nout);
 /* the same dry run for a loaded device weight (its format, act-order, fold range and compute mode included) */
@@ -357,6 +359,67 @@ typedef struct nad_batch_problem {
 void* nad_batch_create(const nad_batch_problem* problems, int n);
 int nad_batch_run(void* batch, void* queue);
 void nad_batch_destroy(void* batch);
+
+/* ===== routed expert matmuls: ne_mul_mat_id / ne_mul_id_ffn_silu (neural_speed/core/ne_layers.c:2384-2462, 7783-7916,
+ * 8053-8075), the FFN of every layer of the Llama graph once n_expert > 0 (models/llama/llama.cpp:620-688).  The
+ * expert of a row is an int32 in DEVICE memory, read inside the launch: nothing here copies ids to the host,
+ * synchronises, allocates or frees, so a routed layer is graph-capturable and a replay follows whatever the router wrote
+ * since.  Activations and outputs are fp32.
+ *
+ * Expert bank: n_expert (1..256) loaded device weights of one shape and format, under nad_batch_create's conditions
+ * -- int4 / int2 tile layouts, no act-order, fp arithmetic, no block mins, no Q6_K, a geometry the M = 1 GEMV takes;
+ * create returns NULL with nad_last_error() naming the offending expert otherwise.  The bank owns one device table of
+ * 64-byte entries (the only allocation of these entries); keep the weights alive while it is. */
+void* nad_expert_bank_create(const void* const* weights, int n_expert);
+/* a geometry-only bank for nad_plan_moe, with the same checks and no GPU needed: geom holds n_expert rows of
+ * [bits (2, 4, 8; 6 = GGUF Q6_K), n, k, blocksize (<= 0: per-channel), NAD_SCALE_*, asym].  It holds no weights: the
+ * launching entries below refuse it (-1). */
+void* nad_expert_bank_plan_only(const int32_t* geom, int n_expert);
+void nad_expert_bank_destroy(void* bank);
+/* [n_expert, bits, n, k, blocksize, scale_t, asym, holds weights]; writes min(nout, 8) values, returns the count or -1 */
+int nad_expert_bank_info(const void* bank, int64_t* out, int nout);
+/* ne_mul_mat_id: out[r][0:n] = act[r][0:k] . W[ids[r * ids_ld + slot]]^T for r < m, ONE launch
+ * (woq_gemv_m1_routed_kernel: workgroups dealt out row by row, each row exactly the arithmetic of its expert's own M = 1
+ * forward -- bit-identical to it).  ids is device memory.  An id outside [0, n_expert) is defined: no weight memory is
+ * touched, the row's activations meet all-zero weights and scales, and the row is written as zeros -- for activations
+ * that are finite and whose fp16 hi part is finite (|x| below 65520); an inf, NaN or larger value gives NaN (0 * inf).  Writes exactly out[0:m, 0:n] whatever out held; reads act only inside
+ * [0:m, 0:k].  Rows need lda % 4 == 0 and a 16-byte aligned base: otherwise -1 before anything is launched.
+ * Every row streams its expert's whole weight, also where several rows chose the same expert: right for decode-size m,
+ * correct but wasteful at prefill sizes (a sorted, grouped GEMM is not part of this library yet). */
+int nad_device_mul_mat_id(const void* bank, const float* act, const int32_t* ids, int ids_ld, int slot, float* out,
+                          int m, int lda, int ldo, void* queue);
+/* The whole routed FFN (llama.cpp:641-679) in three launches.  Problem p = r * top_k + i uses expert e = ids[r * ids_ld
+ * + i]:
+ *   1. t[p] = act1(x_r . G_e^T) * (x_r . U_e^T)   the fused pair epilogue of the M = 1 GEMV, epi = NAD_EPI_SILU_MUL or
+ *                                                  NAD_EPI_GELU_MUL; workspace rows [p][fmid] at offset 0
+ *   2. y[p] = t[p] . D_e^T                          workspace rows [p][fout] at offset round256(m * top_k * fmid * 4)
+ *   3. out[r][n] = ((w[r][0] * y[r * top_k][n]) + w[r][1] * y[r * top_k + 1][n]) + ...   with w[r][i] = wts[r * wts_ld
+ *      + i]: fp32, every product and sum rounded on its own, in slot order (ne_mul then ne_add) -- numpy float32
+ *      reproduces it bit for bit.
+ * t[p] and y[p] are bit-identical to nad_device_ffn_gate_up / nad_device_forward of that expert on that row alone.  A
+ * slot whose id is outside [0, n_expert) has t = y = 0 and contributes w * 0 (finite activations, as above).  The gate
+ * and up banks must agree in K, N, bits, group size, scale type and symmetry; the down bank may differ in format (the
+ * int2 policy keeps it int4, llama_utils.cpp:269-287).  workspace: nad_moe_workspace_size(m, top_k, fmid, fout) = round256(m * top_k * fmid * 4) +
+ * round256(m * top_k * fout * 4) bytes (round256: up to a multiple of 256), 16-byte aligned.  The window contract of
+ * nad_device_mul_mat_id holds for act and out. */
+size_t nad_moe_workspace_size(int m, int top_k, int fmid, int fout);
+int nad_device_moe_ffn(const void* gate_bank, const void* up_bank, const void* down_bank, const float* act,
+                       const int32_t* ids, int ids_ld, const float* wts, int wts_ld, int top_k, int epi,
+                       void* workspace, float* out, int m, int lda, int ldo, void* queue);
+/* The router (llama.cpp:624-638), one wave per row, n_expert <= 64, 1 <= top_k <= n_expert, all in fp32:
+ *   p = softmax(logits[r]) with the row maximum subtracted: expf(x - max) / sum, the sum a butterfly over the lanes
+ *   ids[r][0:top_k] = the indices of the top_k largest p in descending order, a tie going to the lower index
+ *   wts[r][i] = p[ids[r][i]] / (p[ids[r][0]] + p[ids[r][1]] + ...), the sum added in slot order
+ * It is defined by this arithmetic and is NOT the reference's ne_soft_max, whose expf reads an fp16 table
+ * (ne_layers.c): weights agree with it to fp16 table precision only, and near-ties may order differently. */
+int nad_moe_route(const float* logits, int ld, int m, int n_expert, int top_k, int32_t* ids, int ids_ld, float* wts,
+                  int wts_ld, void* queue);
+/* Dry run of nad_device_moe_ffn (no launch, no GPU needed; geometry-only banks qualify): per launch [kernel
+ * NAD_KERNEL_*, grid, threads per workgroup, dynamic LDS bytes] -- 1 gate + up, 2 down (both NAD_KERNEL_GEMV_ROUTED,
+ * grid = m * top_k * workgroups per problem), 3 combine -- then the launch count: 13 values.  Writes min(nout, 13),
+ * returns the number written or -1. */
+int nad_plan_moe(const void* gate_bank, const void* up_bank, const void* down_bank, int m, int top_k, int64_t* out,
+                 int nout);
 
 #ifdef __cplusplus
 }

@@ -104,6 +104,15 @@ SIGNATURES = {
     "nad_batch_create": (_p, [_p, _i]),
     "nad_batch_run": (_i, [_p, _p]),
     "nad_batch_destroy": (None, [_p]),
+    "nad_expert_bank_create": (_p, [_p, _i]),
+    "nad_expert_bank_plan_only": (_p, [_p, _i]),
+    "nad_expert_bank_destroy": (None, [_p]),
+    "nad_expert_bank_info": (_i, [_p, _p, _i]),
+    "nad_device_mul_mat_id": (_i, [_p, _p, _p, _i, _i, _p, _i, _i, _i, _p]),
+    "nad_moe_workspace_size": (_sz, [_i, _i, _i, _i]),
+    "nad_device_moe_ffn": (_i, [_p, _p, _p, _p, _p, _i, _p, _i, _i, _i, _p, _p, _i, _i, _i, _p]),
+    "nad_moe_route": (_i, [_p, _i, _i, _i, _i, _p, _i, _p, _i, _p]),
+    "nad_plan_moe": (_i, [_p, _p, _p, _i, _i, _p, _i]),
     "init_parallel_context": (_p, []),
     "get_tp_size": (_i, [_p]),
     "get_tp_rank": (_i, [_p]),

@@ -11,6 +11,8 @@ Reference entry points mirrored (paths relative to the reference repo root):
                     <- bestla_device_f32f32_forward (ne_bestla.h:97-98) / bestla_f32f32_forward (inner_product.cpp:28-36)
   qkv_forward()     <- bestla_fusion_QKV_f32f32_forward (ip_fusion_qkv.cpp)
   ffn_forward()     <- bestla_fusion_FFN_SiLu_f32f32_forward / _Gelu_Mul_ (ip_fusion_ffn.cpp:734-755)
+  ExpertBank / mul_mat_id() / moe_ffn() / moe_route()
+                    <- ne_mul_mat_id / ne_mul_id_ffn_silu and the router of models/llama/llama.cpp:620-688
   split()           <- TP weight split of model_files.h:1538-1660 (here exact: no re-quantization)
 
 Device buffers are torch tensors (plumbing only); every arithmetic op on the path runs in the HIP kernels.
@@ -170,7 +172,7 @@ def split_range(blob, axis, rank, world, unit=1):
 KERNELS = {1: "woq_gemv_m1_kernel", 2: "woq_gemv_kernel", 3: "woq_skinny_kernel", 4: "woq_i8_kernel",
            5: "woq_gemm3_kernel", 6: "woq_gemm4_kernel", 7: "woq_gemm2_kernel", 8: "woq_gemm_kernel",
            9: "woq_gemm7_kernel", 10: "woq_mid_kernel", 11: "woq_q6k_gemv_kernel", 12: "woq_q6k_gemm_kernel",
-           13: "woq_q6k_i8_kernel"}
+           13: "woq_q6k_i8_kernel", 14: "woq_gemv_m1_routed_kernel", 15: "moe_combine_kernel"}
 
 
 def plan_forward(bits, n, k, group_size=128, scale_dtype="fp16", asym=False, m=1, act="fp32"):
@@ -532,3 +534,141 @@ class Batch:
             except Exception:
                 pass
             self.handle = None
+
+
+# ---------------------------------------------------------------------------------------------------- routed experts
+_SCALE_CODE = {"fp32": 0, "bf16": 1, "fp16": 2}
+
+
+class ExpertBank:
+    """The expert weights of one matmul of a Mixtral-style FFN layer (include/neural_amd.h nad_expert_bank_*): a list of
+    DeviceWeights of one shape and format, held as one device table the routed kernel indexes with ids it reads on the
+    device.  The weights are kept alive with the bank."""
+
+    def __init__(self, weights, _handle=None):
+        self._keep = list(weights)
+        if _handle is None:
+            arr = (C.c_void_p * len(self._keep))(*[C.cast(w.desc, C.c_void_p) for w in self._keep])
+            _handle = lib().nad_expert_bank_create(arr, len(self._keep))
+            if not _handle:
+                raise RuntimeError(f"nad_expert_bank_create failed: {last_error()}")
+        self.handle = _handle
+        o = np.zeros(8, np.int64)
+        if lib().nad_expert_bank_info(self.handle, _ptr(o), 8) != 8:
+            raise RuntimeError(f"nad_expert_bank_info failed: {last_error()}")
+        (self.n_expert, self.bits, self.n, self.k, self.blocksize, self.scale_t, self.asym, self.has_weights) = (
+            int(v) for v in o)
+
+    @classmethod
+    def plan_only(cls, geometries):
+        """A geometry-only bank for plan_moe (no GPU needed, the same checks as a real bank): geometries is a list of
+        (bits, n, k, group_size, scale_dtype, asym) per expert; bits 6 names GGUF Q6_K."""
+        g = np.array([[b, n, k, gs, _SCALE_CODE[st], int(asym)] for b, n, k, gs, st, asym in geometries], np.int32)
+        h = lib().nad_expert_bank_plan_only(_ptr(g), len(g))
+        if not h:
+            raise RuntimeError(f"nad_expert_bank_plan_only failed: {last_error()}")
+        return cls([], _handle=h)
+
+    def __del__(self):
+        h = getattr(self, "handle", None)
+        if h:
+            try:
+                lib().nad_expert_bank_destroy(h)
+            except Exception:
+                pass
+            self.handle = None
+
+
+def mul_mat_id(bank, x, ids, slot, out=None, stream=None):
+    """ne_mul_mat_id: out[r] = x[r] . W[ids[r][slot]]^T in one launch; x cuda fp32 [M][K], ids cuda int32 [M][>slot],
+    read on the device (an id outside the bank gives a zero row)."""
+    torch = _torch()
+    m, k = x.shape
+    assert k == bank.k, (k, bank.k)
+    assert ids.dtype == torch.int32 and ids.shape[0] == m, (ids.dtype, ids.shape)
+    if out is None:
+        out = torch.empty((m, bank.n), dtype=torch.float32, device=x.device)
+    check(lib().nad_device_mul_mat_id(bank.handle, _ptr(x), _ptr(ids), ids.stride(0), slot, _ptr(out), m, x.stride(0),
+                                      out.stride(0), _stream(stream)), "nad_device_mul_mat_id")
+    return out
+
+
+_MOE_WS = {}
+
+
+def moe_workspace(m, top_k, fmid, fout, device, stream=None):
+    """The fp32 workspace moe_ffn uses when the caller gives none, with its two row blocks: (buffer, t [m * top_k][fmid],
+    y [m * top_k][fout]).  One buffer per (shape, device, stream), kept for the life of the process: calls on one stream
+    are ordered and may share it, calls on different streams get their own.  It is allocated at the first call of its
+    key, so make that call outside graph capture (a buffer first allocated inside a capture would come from the
+    graph's private pool and outlive it here), or pass moe_ffn a workspace of your own."""
+    torch = _torch()
+    s = stream if stream is not None else torch.cuda.current_stream()
+    key = (m, top_k, fmid, fout, str(device), int(s.cuda_stream))
+    if key not in _MOE_WS:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("moe_ffn: the first call of a shape on a stream allocates its workspace; make it outside "
+                               "graph capture or pass workspace=")
+        _MOE_WS[key] = moe_workspace_alloc(m, top_k, fmid, fout, device)
+    return (_MOE_WS[key],) + moe_workspace_rows(_MOE_WS[key], m, top_k, fmid, fout)
+
+
+def moe_workspace_alloc(m, top_k, fmid, fout, device="cuda"):
+    """A workspace of nad_moe_workspace_size(m, top_k, fmid, fout) bytes for moe_ffn(..., workspace=)."""
+    torch = _torch()
+    return torch.empty(lib().nad_moe_workspace_size(m, top_k, fmid, fout) // 4, dtype=torch.float32, device=device)
+
+
+def moe_workspace_rows(ws, m, top_k, fmid, fout):
+    """The two row blocks of a moe_ffn workspace: (t [m * top_k][fmid], y [m * top_k][fout]) as views."""
+    p = m * top_k
+    off = (p * fmid * 4 + 255) // 256 * 64
+    return ws[:p * fmid].view(p, fmid), ws[off:off + p * fout].view(p, fout)
+
+
+def moe_ffn(gate, up, down, x, ids, wts, act="silu", out=None, stream=None, workspace=None):
+    """The routed FFN of llama.cpp:641-679 in three launches (nad_device_moe_ffn): out[r] = sum_i wts[r][i] *
+    ((act(x_r . G_e^T) * (x_r . U_e^T)) . D_e^T), e = ids[r][i], slots summed in order.  gate / up / down: ExpertBanks;
+    ids int32 [M][top_k] and wts fp32 [M][top_k] cuda tensors (row strides honoured), read on the device.  workspace: an
+    fp32 cuda tensor of at least nad_moe_workspace_size bytes (moe_workspace_alloc) that no concurrent call uses; None
+    takes the one moe_workspace holds for this shape and stream."""
+    torch = _torch()
+    m, fin = x.shape
+    top_k = ids.shape[1]
+    assert fin == gate.k and ids.dtype == torch.int32 and wts.dtype == torch.float32
+    assert ids.shape[0] == m and tuple(wts.shape) == (m, top_k), (ids.shape, wts.shape)
+    if out is None:
+        out = torch.empty((m, down.n), dtype=torch.float32, device=x.device)
+    if workspace is None:
+        workspace = moe_workspace(m, top_k, gate.n, down.n, x.device, stream)[0]
+    need = lib().nad_moe_workspace_size(m, top_k, gate.n, down.n)
+    assert workspace.dtype == torch.float32 and workspace.is_contiguous() and workspace.numel() * 4 >= need, need
+    ws = workspace
+    epi = EPI_SILU_MUL if act == "silu" else EPI_GELU_MUL
+    check(lib().nad_device_moe_ffn(gate.handle, up.handle, down.handle, _ptr(x), _ptr(ids), ids.stride(0), _ptr(wts),
+                                   wts.stride(0), top_k, epi, _ptr(ws), _ptr(out), m, x.stride(0), out.stride(0),
+                                   _stream(stream)), "nad_device_moe_ffn")
+    return out
+
+
+def moe_route(logits, top_k, stream=None):
+    """The router (nad_moe_route): softmax of each row of logits (cuda fp32 [M][n_expert <= 64]), the top_k experts
+    in descending order (a tie to the lower index) and their weights renormalised to sum 1 -> (ids int32, wts fp32)."""
+    torch = _torch()
+    m, ne = logits.shape
+    ids = torch.empty((m, top_k), dtype=torch.int32, device=logits.device)
+    wts = torch.empty((m, top_k), dtype=torch.float32, device=logits.device)
+    check(lib().nad_moe_route(_ptr(logits), logits.stride(0), m, ne, top_k, _ptr(ids), top_k, _ptr(wts), top_k,
+                              _stream(stream)), "nad_moe_route")
+    return ids, wts
+
+
+def plan_moe(gate, up, down, m, top_k):
+    """What moe_ffn launches for m rows (nad_plan_moe: no launch, no GPU needed; plan-only banks qualify): a list of
+    dict(kernel, grid, threads, lds), one per launch."""
+    o = np.zeros(13, np.int64)
+    if lib().nad_plan_moe(gate.handle, up.handle, down.handle, m, top_k, _ptr(o), 13) != 13:
+        raise RuntimeError(f"nad_plan_moe failed: {last_error()}")
+    n = int(o[12])
+    return [dict(kernel=KERNELS.get(int(o[4 * i]), str(int(o[4 * i]))), grid=int(o[4 * i + 1]),
+                 threads=int(o[4 * i + 2]), lds=int(o[4 * i + 3])) for i in range(n)]

@@ -91,7 +91,7 @@ static void skinny_geometry(int total_stripes, int nt, int nwi, int* ks, int* tp
   *ch = t <= 4 ? 4 : 8;
 }
 
-static int device_cus() {
+int device_cus() {
   static int n = 0;
   if (n == 0) {
     int dev = 0;
@@ -166,6 +166,21 @@ static int prepare_gemv(GemvArgs& a, int& waves, int& grid, const Act& x, const 
   for (int i = 0; i < W.nw; i++)
     if (uint64_t(W[i].ns) * W[i].nt * 1024 >= (1ull << 30)) return 0;
   return 1;
+}
+
+// One M = 1 fp32 problem on ws[0] (nw = 1), or on the {gate, up} pair ws[0], ws[1] with a dual epilogue (nw = 2), as
+// its own decode launch prepares it (capi_moe.hip: the routed launch runs every problem at exactly this geometry).  The
+// pointers in `a` are placeholders.
+bool prepare_m1_problem(GemvArgs& a, int& waves, const DeviceWeight* const* ws, int nw, int epi) {
+  const float* act = reinterpret_cast<const float*>(uintptr_t(1) << 42);  // aligned, never dereferenced on the host
+  float* y = reinterpret_cast<float*>(uintptr_t(1) << 43);
+  float* outs[2] = {y, y};
+  const int ldos[2] = {ws[0]->n, ws[0]->n};
+  Epi e;
+  e.kind = epi;
+  int grid = 0;
+  return prepare_gemv(a, waves, grid, Act{act, kActF32, ws[0]->k, 1, ws[0]->k}, Weights{nw, ws, outs, ldos}, e) &&
+         gemv_uses_m1(a, ws[0]->bits, waves);
 }
 
 // 1 launched, 0 not eligible, -1 launch error

@@ -1,5 +1,6 @@
 // capi_internal.h -- what the units behind the extern "C" boundary share: capi.hip (errors, knobs, dry runs, device
-// context, workspace, compute mode), capi_load.hip, capi_forward.hip, capi_host.hip.  Nothing here is exported.
+// context, workspace, compute mode), capi_load.hip, capi_forward.hip, capi_host.hip, capi_moe.hip.  Nothing here is
+// exported.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -151,6 +152,12 @@ struct Out {
 int ffn_forward(const void* act, int act_dtype, const void* w1p, const void* w2p, const void* w3p, float* tmp1,
                 float* tmp2, float* out, int m, int fin, int fmid, int fout, int lda, int epi, void* queue,
                 bool f16_tmp);
+
+// capi_forward.hip, for capi_moe.hip: the chip's compute units (256 without a device), and the GemvArgs / waves of one
+// M = 1 fp32 problem on ws[0] or on the {gate, up} pair with a dual epilogue, exactly as that problem's own decode
+// launch prepares them; false where the M = 1 GEMV does not take the geometry
+int device_cus();
+bool prepare_m1_problem(nad::GemvArgs& a, int& waves, const nad::DeviceWeight* const* ws, int nw, int epi);
 
 #pragma GCC visibility pop
 

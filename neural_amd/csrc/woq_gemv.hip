@@ -923,6 +923,42 @@ __global__ __launch_bounds__(1024) void woq_gemv_m1_dual_kernel(GemvArgs a, Gemv
     m1_body<B2, G2, AT, false, K2, 1, false, NAD_M1_DUAL_NST>(b, int(blockIdx.x) - ga);
 }
 
+// Routed: the batched launch with the problem table replaced by a lookup the kernel does itself (ne_mul_mat_id,
+// ne_layers.c:7783-7916: per row an int32 id picks one of n_as expert weights).  Workgroup b serves problem
+// p = b / wpp of one shape -- row r = p / slots, slot i = p % slots -- reads that problem's expert id from device
+// memory, takes the expert's tiles / scales / zero points (and the up weight's, for the {gate, up} pair) from the bank
+// entry, derives its activation and output vectors from r, p and the strides, and runs m1_body on its share b % wpp of
+// the stripes: each stripe exactly the arithmetic of the expert's own one-problem launch.  The routing is data of the
+// launch, not of the host call, so a captured graph follows ids that change between replays.
+// An id outside [0, n_expert) is clamped before the table is touched and the problem runs with zero stripes in its
+// weight views: cursor_stripe then builds zero-record resources (the rsrc(ptr, 0) of idle waves), every weight, scale
+// and zero-point load returns zero without touching memory, and the problem writes zeros.
+template <int BITS, int GPT, bool ASYM, int KSN, int SPW, int NST, int ST>
+__global__ __launch_bounds__((m1_max_threads<GPT, KSN>())) void woq_gemv_m1_routed_kernel(GemvArgs a, GemvRouted r) {
+  int bid = int(blockIdx.x);
+  const int p = bid / r.wpp;
+  bid -= p * r.wpp;
+  const int row = p / r.slots;
+  const int id = __builtin_amdgcn_readfirstlane(r.ids[size_t(row) * r.ids_ld + r.ids_col + (p - row * r.slots)]);
+  const bool valid = unsigned(id) < unsigned(r.n_expert);
+  const int e = min(max(id, 0), r.n_expert - 1);
+  const GemvExpertEnt g = r.bank[0][e];
+  a.A = r.act + size_t(r.act_per_slot ? p : row) * r.act_ld;
+  a.w[0].tiles = g.tiles;
+  a.w[0].scales = g.scales;
+  a.w[0].zps = g.zps;
+  a.w[0].out = r.out + size_t(p) * r.out_ld;
+  if (a.dual) {
+    const GemvExpertEnt u = r.bank[1][e];
+    a.w[1].tiles = u.tiles;
+    a.w[1].scales = u.scales;
+    a.w[1].zps = u.zps;
+    a.w[1].out = a.w[0].out;
+  }
+  if (!valid) a.w[0].ns = a.w[1].ns = 0;
+  m1_body<BITS, GPT, kActF32, ASYM, KSN, SPW, false, NST, ST>(a, bid);
+}
+
 // ------------------------------------------------------------------------------------------------ M = 1, specialised
 // The same stream and the same sums as m1_body for the launches a decode token is made of, with the code a launch runs
 // where no memory latency hides it cut down (tools/gemv_path_bytes.py prints it per instantiation):
@@ -1477,6 +1513,61 @@ hipError_t launch_gemv(const GemvArgs& a, int bits, int waves, int grid, size_t 
 }
 
 #endif  // GEMV_PART 0
+
+// woq_gemv_m1_routed_kernel.  fp32 activations only; the K-slice geometry is that of the expert's own one-problem
+// launch (a.lean_ks / a.lean_spw as prepared for it), so a stripe's sums are the same whichever launch serves it.  Two
+// register stages per wave throughout: a routed problem's workgroups stream from a few stages per wave (one token,
+// the chip's workgroups dealt out over top_k problems) to dozens (several rows), where m1_nst would take two and the
+// batched launch three; one depth keeps the instantiations (their own objects: GEMV_PART=4 int4, GEMV_PART=5 int2)
+// at a quarter of woq_gemv_m1_kernel's.
+constexpr int kRoutedNst = 2;
+template <int BITS, int GPT, bool ASYM, int ST>
+static hipError_t routed_launch2(const GemvArgs& a, const GemvRouted& r, dim3 g, dim3 b, size_t lds, hipStream_t st) {
+  if (a.lean_ks == 1)
+    return launch_big_lds<woq_gemv_m1_routed_kernel<BITS, GPT, ASYM, 1, 1, kRoutedNst, ST>>(g, b, lds, st, a, r);
+  if (a.lean_ks == 2)
+    return launch_big_lds<woq_gemv_m1_routed_kernel<BITS, GPT, ASYM, 2, 1, kRoutedNst, ST>>(g, b, lds, st, a, r);
+  return a.lean_spw == 4
+             ? launch_big_lds<woq_gemv_m1_routed_kernel<BITS, GPT, ASYM, KS, 4, kRoutedNst, ST>>(g, b, lds, st, a, r)
+             : launch_big_lds<woq_gemv_m1_routed_kernel<BITS, GPT, ASYM, KS, 2, kRoutedNst, ST>>(g, b, lds, st, a, r);
+}
+#if !defined(GEMV_PART) || GEMV_PART == 5
+// int2: the scale type at compile time, as woq_gemv_m1_kernel's int2 instantiations
+template <int GPT, bool ASYM>
+static hipError_t routed_launch_b2g(const GemvArgs& a, const GemvRouted& r, dim3 g, dim3 b, size_t lds, hipStream_t st) {
+  if (a.scale_t == kScaleF32) return routed_launch2<2, GPT, ASYM, NAD_INT2_ST ? kScaleF32 : -1>(a, r, g, b, lds, st);
+  if (a.scale_t == kScaleBF16) return routed_launch2<2, GPT, ASYM, NAD_INT2_ST ? kScaleBF16 : -1>(a, r, g, b, lds, st);
+  return routed_launch2<2, GPT, ASYM, NAD_INT2_ST ? kScaleF16 : -1>(a, r, g, b, lds, st);
+}
+hipError_t gemv_routed_launch_b2(const GemvArgs& a, const GemvRouted& r, int gpt, dim3 g, dim3 b, size_t lds,
+                                 hipStream_t st) {
+  if (gpt == 4 && !a.asym) return routed_launch_b2g<4, false>(a, r, g, b, lds, st);
+  if (gpt != 1 && gpt != 2) return hipErrorInvalidValue;
+  return by_asym(a, [&](auto as) {
+    return gpt == 1 ? routed_launch_b2g<1, as.value>(a, r, g, b, lds, st) : routed_launch_b2g<2, as.value>(a, r, g, b, lds, st);
+  });
+}
+#else
+hipError_t gemv_routed_launch_b2(const GemvArgs& a, const GemvRouted& r, int gpt, dim3 g, dim3 b, size_t lds,
+                                 hipStream_t st);
+#endif
+#if !defined(GEMV_PART) || GEMV_PART == 4
+hipError_t launch_gemv_routed(const GemvArgs& a, const GemvRouted& r, int bits, int waves, int grid, size_t lds,
+                              hipStream_t stream) {
+  int tpg = 0;
+  const int gpt = gemv_groups_per_tile(bits, a.nt, a.ng, a.bs, &tpg);
+  if (gpt == 0 || a.batch || a.act_t != kActF32 || r.wpp <= 0 || r.slots <= 0 || r.n_expert <= 0 ||
+      !lean_ok(a, bits, waves))
+    return hipErrorInvalidValue;
+  const dim3 g(grid), b(waves * 64);
+  if (bits == 2) return gemv_routed_launch_b2(a, r, gpt, g, b, lds, stream);
+  if (bits != 4 || (gpt != 1 && gpt != 2)) return hipErrorInvalidValue;
+  return by_asym(a, [&](auto as) {
+    return gpt == 1 ? routed_launch2<4, 1, as.value, -1>(a, r, g, b, lds, stream)
+                    : routed_launch2<4, 2, as.value, -1>(a, r, g, b, lds, stream);
+  });
+}
+#endif
 
 }  // namespace nad
 

@@ -145,6 +145,53 @@ struct GemvArgs {
   int m1_spec;                // M = 1 launches may take woq_gemv_m1s_kernel (NAD_GEMV_M1_SPEC; 0: always the kernel above)
 };
 
+// Routed M = 1 launch (woq_gemv_m1_routed_kernel; nad_device_mul_mat_id / nad_device_moe_ffn: ne_mul_mat_id,
+// ne_layers.c:7783-7916).  One expert of a bank: 64 B per entry (one scalar-cache line).
+struct GemvExpertEnt {
+  const void* tiles;
+  const void* scales;
+  const int8_t* zps;
+  const void* pad[5];
+};
+// What the routed kernel takes beside the GemvArgs of ONE problem of the bank's shape.  Workgroup b serves problem
+// p = b / wpp (row r = p / slots, slot i = p % slots) and that problem's share b % wpp of the stripes; the expert is
+// ids[r * ids_ld + ids_col + i], read on the device.
+struct GemvRouted {
+  const GemvExpertEnt* bank[2];  // [0] the weight (gate of a pair), [1] the pair's up weight (dual launches only)
+  int n_expert;
+  int wpp;               // workgroups per problem; GemvArgs::u_q / u_r split one problem's units over them
+  const int32_t* ids;
+  int ids_ld, ids_col;
+  int slots;             // problems per row (1: nad_device_mul_mat_id, top_k: nad_device_moe_ffn)
+  int act_per_slot;      // activation vector of problem p: act + (act_per_slot ? p : r) * act_ld
+  const float* act;
+  int act_ld;
+  float* out;            // output vector of problem p: out + p * out_ld
+  int out_ld;
+};
+// out[r][n] = ((w[r][0] * y[r * top_k][n]) + w[r][1] * y[r * top_k + 1][n]) + ...: separate fp32 multiplies and adds
+// in slot order (ne_mul then ne_add, llama.cpp:676-679)
+struct MoeCombineArgs {
+  const float* y;   // [m * top_k][ldy]
+  int ldy;
+  const float* wts;
+  int wts_ld;
+  int top_k;
+  float* out;
+  int ldo, m, n;
+};
+hipError_t launch_moe_combine(const MoeCombineArgs& a, hipStream_t stream);
+// softmax -> top_k -> renormalise, one wave per row, n_expert <= 64 (nad_moe_route)
+struct MoeRouteArgs {
+  const float* logits;
+  int ld, m, n_expert, top_k;
+  int32_t* ids;
+  int ids_ld;
+  float* wts;
+  int wts_ld;
+};
+hipError_t launch_moe_route(const MoeRouteArgs& a, hipStream_t stream);
+
 // The arguments of woq_gemv_m1s_kernel: only what that kernel reads, with everything that is constant per launch
 // worked out by launch_gemv (K-slices per stripe, units per workgroup).  NWS: weights in the launch (1; 3 = fused QKV;
 // 2 = the {gate, up} pair of the SiLU*mul epilogue).
@@ -344,5 +391,8 @@ hipError_t launch_gemv_dual(const GemvArgs& a, const GemvArgs& b, int ga, int gb
                             hipStream_t stream);
 // the batched M = 1 launch (requires gemv_uses_m1; grid = problems * a.batch_wpp)
 hipError_t launch_gemv_batch(const GemvArgs& a, int bits, int waves, int grid, size_t lds, hipStream_t stream);
+// the routed M = 1 launch (requires gemv_uses_m1 and fp32 activations; grid = problems * r.wpp)
+hipError_t launch_gemv_routed(const GemvArgs& a, const GemvRouted& r, int bits, int waves, int grid, size_t lds,
+                              hipStream_t stream);
 
 }  // namespace nad
