@@ -194,6 +194,10 @@ int nad_device_forward(const void* act, int act_dtype, const void* devstor, floa
 #define NAD_KERNEL_Q6K_I8 13   /* woq_q6k_i8_kernel: GGUF Q6_K in mode NAD_COMPUTE_Q8_K, any M (flags bit 0 clear) */
 #define NAD_KERNEL_GEMV_ROUTED 14 /* woq_gemv_m1_routed_kernel: expert matmuls routed on the device (nad_plan_moe) */
 #define NAD_KERNEL_MOE_COMBINE 15 /* moe_combine_kernel: the weighted sum of the slot results (nad_plan_moe) */
+#define NAD_KERNEL_MOE_SORT 16 /* moe_sort_kernel: the problems sorted by expert on the device (nad_plan_moe_grouped) */
+#define NAD_KERNEL_CVT_ACT 17  /* nad_cvt_act_kernel: activations -> fp16, K padded to the K tile (nad_plan_moe_grouped) */
+#define NAD_KERNEL_GEMM7_GROUPED 18 /* woq_gemm7_grouped_kernel: gemm7 over the sorted rows of routed experts */
+#define NAD_KERNEL_MOE_GATHER 19 /* moe_gather_kernel: the slot sum / un-permute over sorted rows (nad_plan_moe_grouped) */
 int nad_plan_forward(int bits, int n, int k, int blocksize, int scale_t, int asym, int m, int act_dtype, int64_t* out,
                      int nout);
 /* the same dry run for a loaded device weight (its format, act-order, fold range and compute mode included) */
@@ -385,7 +389,11 @@ int nad_expert_bank_info(const void* bank, int64_t* out, int nout);
  * that are finite and whose fp16 hi part is finite (|x| below 65520); an inf, NaN or larger value gives NaN (0 * inf).  Writes exactly out[0:m, 0:n] whatever out held; reads act only inside
  * [0:m, 0:k].  Rows need lda % 4 == 0 and a 16-byte aligned base: otherwise -1 before anything is launched.
  * Every row streams its expert's whole weight, also where several rows chose the same expert: right for decode-size m,
- * correct but wasteful at prefill sizes (a sorted, grouped GEMM is not part of this library yet). */
+ * correct but wasteful at prefill sizes: there nad_device_mul_mat_id_grouped / nad_device_moe_ffn_grouped (below) read
+ * every expert's weight once.  The caller chooses; nothing switches between the two forms by itself.  Measured on
+ * Mixtral-8x7B shapes (8 experts, top-2, int4 g128; profiles/moe_grouped_times.txt): the grouped
+ * FFN has a floor of about 220 us per layer call, so this form is ahead at M = 4 (128 us) and behind from M = 16 on
+ * (432 against 222 us; M = 2048: 58.5 against 1.85 ms). */
 int nad_device_mul_mat_id(const void* bank, const float* act, const int32_t* ids, int ids_ld, int slot, float* out,
                           int m, int lda, int ldo, void* queue);
 /* The whole routed FFN (llama.cpp:641-679) in three launches.  Problem p = r * top_k + i uses expert e = ids[r * ids_ld
@@ -420,6 +428,59 @@ int nad_moe_route(const float* logits, int ld, int m, int n_expert, int top_k, i
  * returns the number written or -1. */
 int nad_plan_moe(const void* gate_bank, const void* up_bank, const void* down_bank, int m, int top_k, int64_t* out,
                  int nout);
+
+/* ===== the same, sorted and grouped: for prefill-size m.  The problems p = r * top_k + i (expert e_p = ids[r * ids_ld +
+ * i], valid when 0 <= e_p < n_expert) are sorted by (e_p, p) ON THE DEVICE, and every expert's rows run through gemm7's
+ * tile kernel (woq_gemm7_grouped_kernel: MFMA, the expert's weight read once per 32 .. 256 rows instead of once per
+ * row).  As above nothing copies ids to the host, synchronises, allocates or frees: graph-capturable, and a replay
+ * follows the ids it finds.  The sort is a function of ids alone (a stable counting sort, no atomics).
+ *
+ * A bank is taken when every expert's format is one gemm7 has (recorded at bank creation): int4 groups of 64 or
+ * 128 * 2^j, int2 groups of 64 * 2^j (groups of 32 have no bank: nad_expert_bank_create refuses them), sym or asym, any
+ * scale type, every q * s inside the fp16 range (geometry-only banks count as such).  The FFN also needs fmid to be a whole number of the down bank's K tiles (128
+ * int4, 256 int2).  Anything else: -1 before any launch, nad_last_error() naming the bank and the reason -- never the
+ * row-routed path in its place.
+ *
+ * Arithmetic: the activations are rounded to fp16 and q * s is rounded once to fp16, as in every gemm7 forward; an
+ * output element's MFMA sequence does not depend on the other rows of its tile, so y for (x_r, e) is bit-identical
+ * whatever else is in the batch, whatever the tile height, and to nad_device_forward of expert e on fp16 rows where
+ * that runs gemm7 without split K.  The FFN keeps act1(gate) and act1(gate) * up as fp16 (the dense prefill FFN's
+ * intermediates) and y in fp32.
+ *
+ * Workspace (16-byte aligned, nad_moe_grouped_workspace_size bytes; np = m * top_k; every part starts at the next
+ * multiple of 256 bytes after the one before):
+ *   offs  int32 [n_expert + 1]   expert e owns sorted rows offs[e] .. offs[e + 1] - 1; offs[n_expert] = valid problems
+ *   perm  int32 [np]             the valid problems by (e_p, p); -1 from offs[n_expert] on
+ *   src   int32 [np]             perm[q] / top_k; 0 from offs[n_expert] on
+ *   inv   int32 [np]             the sorted position of p, -1 for an invalid id
+ *   tiles int32 count, 12 bytes unused, then int32 [np / 32 + min(n_expert, np)][4] = (e, q0, q1, 0): per expert
+ *         ceil(count_e / BM) tiles of at most BM sorted rows, BM the call's tile height
+ *   x16   fp16 [m][kp]           the activations, kp = K rounded up to the gate bank's K tile
+ *   t16   fp16 [np][fmid]        FFN only: act1(x . G_e^T) by sorted row
+ *   u16   fp16 [np][fmid]        FFN only: t16 * (x . U_e^T)
+ *   y     fp32 [np][fout]        the sorted result rows (fout: the down bank's N; one matmul: the bank's N)
+ * up_bank = down_bank = NULL sizes the one-matmul form (top_k = 1).  Every word a launch reads is rewritten by the
+ * call; rows of t16 / u16 / y from offs[n_expert] on are not written. */
+size_t nad_moe_grouped_workspace_size(const void* gate_bank, const void* up_bank, const void* down_bank, int m,
+                                      int top_k);
+/* nad_device_moe_ffn's arguments and result contract, in six launches: sort; x -> fp16; gate (act1 -> t16); up (t16 *
+ * product -> u16); down (-> y); out[r][n] = ((w[r][0] * y[inv[r * top_k]][n]) + w[r][1] * y[inv[r * top_k + 1]][n]) +
+ * ... with nad_device_moe_ffn's combine arithmetic, an invalid slot contributing w * 0.0f.  Writes exactly
+ * out[0:m, 0:fout]; reads act only inside [0:m, 0:fin]; rows need lda % 4 == 0 and a 16-byte aligned base. */
+int nad_device_moe_ffn_grouped(const void* gate_bank, const void* up_bank, const void* down_bank, const float* act,
+                               const int32_t* ids, int ids_ld, const float* wts, int wts_ld, int top_k, int epi,
+                               void* workspace, float* out, int m, int lda, int ldo, void* queue);
+/* ne_mul_mat_id grouped: sort (by ids[r * ids_ld + slot]); x -> fp16; one grouped GEMM into y; out[r] = y[inv[r]], or a
+ * zero row for an id outside [0, n_expert).  Same window contract. */
+int nad_device_mul_mat_id_grouped(const void* bank, const float* act, const int32_t* ids, int ids_ld, int slot,
+                                  void* workspace, float* out, int m, int lda, int ldo, void* queue);
+/* Dry run of the grouped entries (no launch, no GPU needed; geometry-only banks qualify): per launch [kernel
+ * NAD_KERNEL_*, grid, threads per workgroup, dynamic LDS bytes], then the tile height BM (gemm7's choice for m * top_k /
+ * n_expert rows, or NAD_GEMM7_BM), the tile bound floor(m * top_k / BM) + min(n_expert, m * top_k) -- a grouped GEMM's
+ * grid is that bound times its column tiles of 128 -- and the launch count.  FFN: 6 launches, 27 values; up_bank =
+ * down_bank = NULL (top_k = 1): 4 launches, 19 values.  Writes min(nout, that), returns the number written or -1. */
+int nad_plan_moe_grouped(const void* gate_bank, const void* up_bank, const void* down_bank, int m, int top_k,
+                         int64_t* out, int nout);
 
 #ifdef __cplusplus
 }

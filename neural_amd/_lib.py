@@ -113,6 +113,10 @@ SIGNATURES = {
     "nad_device_moe_ffn": (_i, [_p, _p, _p, _p, _p, _i, _p, _i, _i, _i, _p, _p, _i, _i, _i, _p]),
     "nad_moe_route": (_i, [_p, _i, _i, _i, _i, _p, _i, _p, _i, _p]),
     "nad_plan_moe": (_i, [_p, _p, _p, _i, _i, _p, _i]),
+    "nad_moe_grouped_workspace_size": (_sz, [_p, _p, _p, _i, _i]),
+    "nad_device_moe_ffn_grouped": (_i, [_p, _p, _p, _p, _p, _i, _p, _i, _i, _i, _p, _p, _i, _i, _i, _p]),
+    "nad_device_mul_mat_id_grouped": (_i, [_p, _p, _p, _i, _i, _p, _p, _i, _i, _i, _p]),
+    "nad_plan_moe_grouped": (_i, [_p, _p, _p, _i, _i, _p, _i]),
     "init_parallel_context": (_p, []),
     "get_tp_size": (_i, [_p]),
     "get_tp_rank": (_i, [_p]),

@@ -172,7 +172,8 @@ def split_range(blob, axis, rank, world, unit=1):
 KERNELS = {1: "woq_gemv_m1_kernel", 2: "woq_gemv_kernel", 3: "woq_skinny_kernel", 4: "woq_i8_kernel",
            5: "woq_gemm3_kernel", 6: "woq_gemm4_kernel", 7: "woq_gemm2_kernel", 8: "woq_gemm_kernel",
            9: "woq_gemm7_kernel", 10: "woq_mid_kernel", 11: "woq_q6k_gemv_kernel", 12: "woq_q6k_gemm_kernel",
-           13: "woq_q6k_i8_kernel", 14: "woq_gemv_m1_routed_kernel", 15: "moe_combine_kernel"}
+           13: "woq_q6k_i8_kernel", 14: "woq_gemv_m1_routed_kernel", 15: "moe_combine_kernel", 16: "moe_sort_kernel",
+           17: "nad_cvt_act_kernel", 18: "woq_gemm7_grouped_kernel", 19: "moe_gather_kernel"}
 
 
 def plan_forward(bits, n, k, group_size=128, scale_dtype="fp16", asym=False, m=1, act="fp32"):
@@ -672,3 +673,130 @@ def plan_moe(gate, up, down, m, top_k):
     n = int(o[12])
     return [dict(kernel=KERNELS.get(int(o[4 * i]), str(int(o[4 * i]))), grid=int(o[4 * i + 1]),
                  threads=int(o[4 * i + 2]), lds=int(o[4 * i + 3])) for i in range(n)]
+
+
+# ------------------------------------------------------------------------------------- routed experts, sorted and grouped
+def _h(bank):
+    return bank.handle if bank is not None else None
+
+
+def moe_grouped_workspace_size(gate, up, down, m, top_k):
+    """nad_moe_grouped_workspace_size: bytes; up = down = None sizes the one-matmul form (top_k = 1)."""
+    return int(lib().nad_moe_grouped_workspace_size(_h(gate), _h(up), _h(down), m, top_k))
+
+
+def moe_grouped_workspace_alloc(gate, up, down, m, top_k, device="cuda"):
+    """A workspace (uint8 cuda tensor) for moe_ffn_grouped(..., workspace=), or with up = down = None for
+    mul_mat_id_grouped.  torch's allocations are 256-byte aligned, which the entries' 16 bytes need."""
+    torch = _torch()
+    size = moe_grouped_workspace_size(gate, up, down, m, top_k)
+    if size == 0:
+        raise RuntimeError(f"nad_moe_grouped_workspace_size failed: {last_error()}")
+    return torch.empty(size, dtype=torch.uint8, device=device)
+
+
+def moe_grouped_workspace_rows(ws, gate, up, down, m, top_k):
+    """Views into a grouped workspace by the layout of include/neural_amd.h: dict(perm int32 [np], offs int32
+    [n_expert + 1], inv int32 [np], src int32 [np], ntiles int32 [1], tiles int32 [bound][4], x16 fp16 [m][kp], y fp32
+    [np][fout], and for the FFN t16 / u16 fp16 [np][fmid])."""
+    torch = _torch()
+    np_, ne = m * top_k, gate.n_expert
+    ktile = 128 if gate.bits == 4 else 256
+    kp = (gate.k + ktile - 1) // ktile * ktile
+    fout = down.n if down is not None else gate.n
+    o = [0]
+
+    def part(nbytes, dtype, shape, skip=0):
+        at = o[0]
+        o[0] += (nbytes + 255) // 256 * 256
+        return ws[at + skip:at + nbytes].view(dtype).view(*shape)
+
+    bound = np_ // 32 + min(ne, np_)
+    r = dict(offs=part((ne + 1) * 4, torch.int32, (ne + 1,)), perm=part(np_ * 4, torch.int32, (np_,)),
+             src=part(np_ * 4, torch.int32, (np_,)), inv=part(np_ * 4, torch.int32, (np_,)))
+    at = o[0]
+    r["tiles"] = part(16 + bound * 16, torch.int32, (bound, 4), skip=16)
+    r["ntiles"] = ws[at:at + 4].view(torch.int32)
+    r["x16"] = part(m * kp * 2, torch.float16, (m, kp))
+    if down is not None:
+        r["t16"] = part(np_ * gate.n * 2, torch.float16, (np_, gate.n))
+        r["u16"] = part(np_ * gate.n * 2, torch.float16, (np_, gate.n))
+    r["y"] = part(np_ * fout * 4, torch.float32, (np_, fout))
+    assert o[0] == moe_grouped_workspace_size(gate, up, down, m, top_k), o[0]
+    return r
+
+
+_MOE_GWS = {}
+
+
+def _grouped_workspace(gate, up, down, m, top_k, device, stream, who):
+    """The workspace the grouped calls use when the caller gives none: one per (banks, shape, device, stream), kept for
+    the life of the process and first allocated outside graph capture (as moe_workspace)."""
+    torch = _torch()
+    s = stream if stream is not None else torch.cuda.current_stream()
+    key = (gate.handle, _h(up), _h(down), m, top_k, str(device), int(s.cuda_stream))
+    if key not in _MOE_GWS:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f"{who}: the first call of a shape on a stream allocates its workspace; make it outside "
+                               "graph capture or pass workspace=")
+        _MOE_GWS[key] = moe_grouped_workspace_alloc(gate, up, down, m, top_k, device)
+    return _MOE_GWS[key]
+
+
+def _check_ws(ws, need):
+    torch = _torch()
+    assert ws.dtype == torch.uint8 and ws.is_contiguous() and ws.numel() >= need and ws.data_ptr() % 16 == 0, need
+
+
+def moe_ffn_grouped(gate, up, down, x, ids, wts, act="silu", out=None, stream=None, workspace=None):
+    """moe_ffn for prefill-size M (nad_device_moe_ffn_grouped): the problems sorted by expert on the device, each
+    expert's rows through the grouped gemm7, six launches.  Same arguments as moe_ffn; workspace: a uint8 cuda tensor
+    of moe_grouped_workspace_size bytes (moe_grouped_workspace_alloc), None takes the one held for this shape and
+    stream.  Banks gemm7 does not take raise (there is no fallback to moe_ffn)."""
+    torch = _torch()
+    m, fin = x.shape
+    top_k = ids.shape[1]
+    assert fin == gate.k and ids.dtype == torch.int32 and wts.dtype == torch.float32
+    assert ids.shape[0] == m and tuple(wts.shape) == (m, top_k), (ids.shape, wts.shape)
+    if workspace is None:
+        workspace = _grouped_workspace(gate, up, down, m, top_k, x.device, stream, "moe_ffn_grouped")
+    if out is None:
+        out = torch.empty((m, down.n), dtype=torch.float32, device=x.device)
+    _check_ws(workspace, moe_grouped_workspace_size(gate, up, down, m, top_k))
+    epi = EPI_SILU_MUL if act == "silu" else EPI_GELU_MUL
+    check(lib().nad_device_moe_ffn_grouped(gate.handle, up.handle, down.handle, _ptr(x), _ptr(ids), ids.stride(0),
+                                           _ptr(wts), wts.stride(0), top_k, epi, _ptr(workspace), _ptr(out), m,
+                                           x.stride(0), out.stride(0), _stream(stream)), "nad_device_moe_ffn_grouped")
+    return out
+
+
+def mul_mat_id_grouped(bank, x, ids, slot, out=None, stream=None, workspace=None):
+    """mul_mat_id for prefill-size M (nad_device_mul_mat_id_grouped): sort, fp16 conversion, one grouped gemm7,
+    un-permute; an id outside the bank gives a zero row."""
+    torch = _torch()
+    m, k = x.shape
+    assert k == bank.k, (k, bank.k)
+    assert ids.dtype == torch.int32 and ids.shape[0] == m, (ids.dtype, ids.shape)
+    if workspace is None:
+        workspace = _grouped_workspace(bank, None, None, m, 1, x.device, stream, "mul_mat_id_grouped")
+    if out is None:
+        out = torch.empty((m, bank.n), dtype=torch.float32, device=x.device)
+    _check_ws(workspace, moe_grouped_workspace_size(bank, None, None, m, 1))
+    check(lib().nad_device_mul_mat_id_grouped(bank.handle, _ptr(x), _ptr(ids), ids.stride(0), slot, _ptr(workspace),
+                                              _ptr(out), m, x.stride(0), out.stride(0), _stream(stream)),
+          "nad_device_mul_mat_id_grouped")
+    return out
+
+
+def plan_moe_grouped(gate, up, down, m, top_k):
+    """What moe_ffn_grouped (up = down = None: mul_mat_id_grouped) launches for m rows (nad_plan_moe_grouped: no launch,
+    no GPU needed; plan-only banks qualify): dict(launches=[dict(kernel, grid, threads, lds), ...], bm, bound)."""
+    o = np.zeros(27, np.int64)
+    c = lib().nad_plan_moe_grouped(_h(gate), _h(up), _h(down), m, top_k, _ptr(o), 27)
+    if c < 3:
+        raise RuntimeError(f"nad_plan_moe_grouped failed: {last_error()}")
+    n = int(o[c - 1])
+    assert c == 4 * n + 3, (c, n)
+    return dict(launches=[dict(kernel=KERNELS.get(int(o[4 * i]), str(int(o[4 * i]))), grid=int(o[4 * i + 1]),
+                               threads=int(o[4 * i + 2]), lds=int(o[4 * i + 3])) for i in range(n)],
+                bm=int(o[4 * n]), bound=int(o[4 * n + 1]))

@@ -605,6 +605,8 @@ static int gemm7_bm(const DeviceWeight& w, int m) {
   const int bm = knobs().gemm7_bm > 0 ? knobs().gemm7_bm : gemm7_pick_bm(w, m);
   return (bm != 32 && bm != 64 && bm != 128) ? 256 : bm;
 }
+int gemm7_tile_height(const DeviceWeight& w, int m) { return gemm7_bm(w, m); }
+int gemm7_k_tile(const DeviceWeight& w) { return k_tile(w); }
 
 // M > 16, one weight: the int8 arithmetic, the mid-M kernel, a pipelined GEMM on the fp16 activations (pre: a copy the
 // caller shares among weights) or the register-staged fallback

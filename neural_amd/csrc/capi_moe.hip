@@ -1,7 +1,9 @@
 // capi_moe.hip -- Mixtral-style expert FFNs with the routing read on the device (include/neural_amd.h, "routed expert
 // matmuls"): the expert bank, nad_device_mul_mat_id (ne_mul_mat_id, ne_layers.c:2384-2462, 7783-7916),
 // nad_device_moe_ffn (models/llama/llama.cpp:641-679), the router (llama.cpp:624-638) and the dry run.  The hot path is
-// woq_gemv_m1_routed_kernel (woq_gemv.hip); the bank's device table is the feature's only allocation.
+// woq_gemv_m1_routed_kernel (woq_gemv.hip); the bank's device table is the feature's only allocation.  For prefill
+// sizes the sorted, grouped entries (nad_device_moe_ffn_grouped, nad_device_mul_mat_id_grouped): moe_sort_kernel
+// (woq_moe.hip), then woq_gemm7_grouped_kernel (woq_gemm7.hip) over every expert's sorted rows.
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -19,6 +21,7 @@ struct NadExpertBank {
   int n_expert = 0;
   DeviceWeight w0{};             // the shape and format every expert shares (its pointers are expert 0's)
   GemvExpertEnt* dev = nullptr;  // [n_expert]; null for a geometry-only bank (nad_expert_bank_plan_only)
+  bool g7_ok = false;            // every expert takes gemm7 (gemm7_ok, stripe-major): the grouped entries serve the bank
 };
 
 const NadExpertBank* as_bank(const void* p, const char* who, const char* role) {
@@ -163,6 +166,10 @@ NadExpertBank* bank_new(const DeviceWeight* const* ws, int n, const char* who) {
   auto* b = new NadExpertBank();
   b->n_expert = n;
   b->w0 = *ws[0];
+  b->g7_ok = true;
+  for (int i = 0; i < n; i++)
+    b->g7_ok = b->g7_ok && !ws[i]->kmajor && ws[i]->blocksize >= 64 &&
+               gemm7_ok(ws[i]->bits, ws[i]->blocksize, ws[i]->fold_ok);
   return b;
 }
 }  // namespace
@@ -361,6 +368,311 @@ extern "C" int nad_plan_moe(const void* gate_bank, const void* up_bank, const vo
                          NAD_KERNEL_MOE_COMBINE, int64_t((fout + 255) / 256) * m, 256, 0,
                          3};
   const int c = std::min(nout, 13);
+  std::memcpy(out, v, sizeof(int64_t) * size_t(c));
+  return c;
+}
+
+// ------------------------------------------------------------------------------------------------ sorted, grouped
+namespace {
+// The workspace of the grouped entries (include/neural_amd.h), every part at a multiple of 256 bytes
+struct GroupedWs {
+  int64_t np = 0;
+  int bound32 = 0, kp = 0, fmid = 0, fout = 0;
+  size_t offs = 0, perm = 0, src = 0, inv = 0, tiles = 0, x16 = 0, t16 = 0, u16 = 0, y = 0, total = 0;
+};
+int tile_bound(int64_t np, int n_expert, int bm) { return int(np / bm + std::min<int64_t>(n_expert, np)); }
+
+// up == down == nullptr: the one-matmul form (x16 and y only)
+GroupedWs grouped_ws(const NadExpertBank& g, const NadExpertBank* down, int m, int top_k) {
+  GroupedWs w;
+  w.np = int64_t(m) * top_k;
+  w.bound32 = tile_bound(w.np, g.n_expert, 32);
+  w.kp = g.w0.nt * gemm7_k_tile(g.w0);
+  w.fmid = down ? g.w0.n : 0;
+  w.fout = down ? down->w0.n : g.w0.n;
+  size_t o = 0;
+  auto part = [&](uint64_t bytes) {
+    const size_t at = o;
+    o += size_t(align256(bytes));
+    return at;
+  };
+  const uint64_t np = uint64_t(w.np);
+  w.offs = part(uint64_t(g.n_expert + 1) * 4);
+  w.perm = part(np * 4);
+  w.src = part(np * 4);
+  w.inv = part(np * 4);
+  w.tiles = part(16 + uint64_t(w.bound32) * 16);
+  w.x16 = part(uint64_t(m) * w.kp * 2);
+  if (down) {
+    w.t16 = part(np * w.fmid * 2);
+    w.u16 = part(np * w.fmid * 2);
+  }
+  w.y = part(np * w.fout * 4);
+  w.total = o;
+  return w;
+}
+
+bool grouped_bank_ok(const NadExpertBank& b, const char* who, const char* role) {
+  if (b.g7_ok) return true;
+  set_err("%s: the %s bank (int%d, groups of %d%s) does not take the grouped gemm7: it needs int4 groups of 64 or 128 * 2^j, or "
+          "int2 groups of 64 * 2^j, stripe-major, with every q * s in fp16 range",
+          who, role, b.w0.bits, b.w0.blocksize, b.w0.kmajor ? ", K-major" : "");
+  return false;
+}
+
+// One grouped launch's shape: the tile height is one for the whole call (the sort writes one tile table)
+struct GroupedGeom {
+  int bm = 0, bound = 0;
+};
+bool grouped_geometry(GroupedGeom& g, const NadExpertBank& first, const NadExpertBank* const* banks, int nb, int m,
+                      int top_k, const GroupedWs& ws, const char* who) {
+  const int64_t np = ws.np;
+  if (np >= (int64_t(1) << 30) || uint64_t(m) * ws.kp * 2 >= (1ull << 32) ||
+      uint64_t(np) * std::max(ws.fmid, 1) * 2 >= (1ull << 32)) {
+    set_err("%s: %lld problems of these shapes are more than one launch addresses", who, static_cast<long long>(np));
+    return false;
+  }
+  // the height gemm7 picks for an expert's mean share of the rows
+  g.bm = gemm7_tile_height(first.w0, int((np + first.n_expert - 1) / first.n_expert));
+  g.bound = tile_bound(np, first.n_expert, g.bm);
+  for (int i = 0; i < nb; i++)
+    if (int64_t(g.bound) * ((banks[i]->w0.ns + 7) / 8) >= (int64_t(1) << 31)) {
+      set_err("%s: %lld problems are more than one launch takes", who, static_cast<long long>(np));
+      return false;
+    }
+  return true;
+}
+
+SkinnyWeight bank_view(const NadExpertBank& b, float* out, int ldo) {
+  const DeviceWeight& w = b.w0;
+  SkinnyWeight v{};
+  v.tiles = w.tiles;  // expert 0's; the kernel takes every tile's own from the bank's table
+  v.scales = w.scales;
+  v.zps = w.zps;
+  v.n = w.n;
+  v.ns = w.ns;
+  v.nt = w.nt;
+  v.ng = w.ng;
+  v.bs = w.blocksize;
+  v.ldo = ldo;
+  v.out = out;
+  v.f4 = -1;
+  return v;
+}
+
+struct GroupedPtrs {
+  int32_t *offs, *perm, *src, *inv, *ntiles;
+  int4* tiles;
+  _Float16 *x16, *t16, *u16;
+  float* y;
+};
+GroupedPtrs grouped_ptrs(void* workspace, const GroupedWs& w) {
+  char* b = static_cast<char*>(workspace);
+  auto i32 = [&](size_t o) { return reinterpret_cast<int32_t*>(b + o); };
+  auto h16 = [&](size_t o) { return reinterpret_cast<_Float16*>(b + o); };
+  return GroupedPtrs{i32(w.offs), i32(w.perm), i32(w.src), i32(w.inv), i32(w.tiles),
+                     reinterpret_cast<int4*>(b + w.tiles + 16), h16(w.x16), h16(w.t16), h16(w.u16),
+                     reinterpret_cast<float*>(b + w.y)};
+}
+
+// One grouped GEMM of the call.  lds: the dry run's record of the instantiation's dynamic LDS.
+struct GroupedOp {
+  const NadExpertBank* bank;
+  const _Float16* A16;
+  int lda16;
+  const int32_t* rows;
+  int epi;
+  _Float16* out16;
+  const _Float16* aux16;
+  float* out;
+};
+int run_grouped(const GroupedOp& op, const GroupedGeom& g, const GroupedPtrs& p, hipStream_t st, int64_t* plan4) {
+  const DeviceWeight& w = op.bank->w0;
+  GemmArgs a{};
+  a.K = w.k;
+  a.scale_t = w.scale_t;
+  a.epi = op.epi;
+  a.fold = 1;
+  a.ld_aux = w.n;
+  a.out16 = op.out16;
+  a.ldo16 = w.n;
+  a.aux16 = op.aux16;
+  a.w = bank_view(*op.bank, op.out, w.n);
+  const GemmGrouped gg{op.bank->dev, p.tiles, p.ntiles, op.rows};
+  const int grid = g.bound * ((w.ns + 7) / 8);
+  if (plan4) {
+    int lds = 0;
+    (void)launch_gemm7_grouped(a, gg, w.bits, g.bm, grid, nullptr, 0, nullptr, &lds);
+    plan4[0] = NAD_KERNEL_GEMM7_GROUPED;
+    plan4[1] = grid;
+    plan4[2] = 512;
+    plan4[3] = lds;
+    return 0;
+  }
+  return launch(false, "grouped gemm7 kernel",
+                [&] { return launch_gemm7_grouped(a, gg, w.bits, g.bm, grid, op.A16, op.lda16, st, nullptr); })
+             ? 0
+             : -1;
+}
+
+int gate_epi(int dual) { return dual == kEpiSiluMul ? kEpiSilu : kEpiGelu; }
+
+// what the FFN entry and its dry run check alike; fills ws and g
+bool grouped_ffn_ok(const NadExpertBank& gb, const NadExpertBank& ub, const NadExpertBank& db, int m, int top_k,
+                    GroupedWs& ws, GroupedGeom& g, const char* who) {
+  if (!pair_ok(gb, ub, db, who)) return false;
+  if (!grouped_bank_ok(gb, who, "gate") || !grouped_bank_ok(ub, who, "up") || !grouped_bank_ok(db, who, "down"))
+    return false;
+  const int fmid = gb.w0.n, kt = gemm7_k_tile(db.w0);
+  if (db.w0.nt * kt != fmid || fmid % 8 != 0) {
+    set_err("%s: fmid (%d) is not a whole number of the down bank's K tiles (%d deep): the fp16 intermediate cannot be "
+            "its operand as it lies", who, fmid, kt);
+    return false;
+  }
+  ws = grouped_ws(gb, &db, m, top_k);
+  const NadExpertBank* banks[3] = {&gb, &ub, &db};
+  return grouped_geometry(g, gb, banks, 3, m, top_k, ws, who);
+}
+}  // namespace
+
+extern "C" size_t nad_moe_grouped_workspace_size(const void* gate_bank, const void* up_bank, const void* down_bank,
+                                                 int m, int top_k) {
+  const char* who = "nad_moe_grouped_workspace_size";
+  const NadExpertBank* gb = as_bank(gate_bank, who, "gate");
+  if (!gb || m <= 0 || top_k <= 0) return 0;
+  const NadExpertBank* db = nullptr;
+  if (up_bank || down_bank) {
+    if (!as_bank(up_bank, who, "up") || !(db = as_bank(down_bank, who, "down"))) return 0;
+  }
+  return grouped_ws(*gb, db, m, top_k).total;
+}
+
+extern "C" int nad_device_moe_ffn_grouped(const void* gate_bank, const void* up_bank, const void* down_bank,
+                                          const float* act, const int32_t* ids, int ids_ld, const float* wts,
+                                          int wts_ld, int top_k, int epi, void* workspace, float* out, int m, int lda,
+                                          int ldo, void* queue) {
+  const char* who = "nad_device_moe_ffn_grouped";
+  const NadExpertBank* gb = as_bank(gate_bank, who, "gate");
+  const NadExpertBank* ub = gb ? as_bank(up_bank, who, "up") : nullptr;
+  const NadExpertBank* db = ub ? as_bank(down_bank, who, "down") : nullptr;
+  if (!db) return -1;
+  if (epi != kEpiSiluMul && epi != kEpiGeluMul) {
+    set_err("%s: the epilogue must be SILU_MUL or GELU_MUL", who);
+    return -1;
+  }
+  const int fin = gb->w0.k, fmid = gb->w0.n, fout = db->w0.n;
+  if (!act || !ids || !wts || !workspace || !out || m < 0 || top_k < 1 || top_k > ids_ld || top_k > wts_ld ||
+      ldo < fout || reinterpret_cast<uintptr_t>(workspace) % 16 != 0) {
+    set_err("%s: bad arguments (m=%d top_k=%d ids_ld=%d wts_ld=%d ldo=%d fout=%d; the workspace 16-B aligned)", who, m,
+            top_k, ids_ld, wts_ld, ldo, fout);
+    return -1;
+  }
+  GroupedWs ws;
+  GroupedGeom g;
+  if (!grouped_ffn_ok(*gb, *ub, *db, std::max(m, 1), top_k, ws, g, who)) return -1;
+  if (!rows_ok(act, lda, fin, who) || !launchable(*gb, who) || !launchable(*ub, who) || !launchable(*db, who)) return -1;
+  if (m == 0) return 0;
+  hipStream_t st = static_cast<hipStream_t>(queue);
+  const GroupedPtrs p = grouped_ptrs(workspace, ws);
+  // launch 1: the sort
+  const MoeSortArgs sa{ids, ids_ld, m, top_k, gb->n_expert, g.bm, p.offs, p.perm, p.src, p.inv, p.tiles, p.ntiles};
+  if (!launch(false, "moe sort kernel", [&] { return launch_moe_sort(sa, st); })) return -1;
+  // launch 2: x -> fp16 [m][kp], zeros past fin
+  if (!launch(false, "activation conversion",
+              [&] { return launch_cvt_act(act, kActF32, lda, m, fin, ws.kp, nullptr, p.x16, st); }))
+    return -1;
+  // launches 3-5: t16[q] = act1(x_src[q] . G_e^T); u16[q] = t16[q] * (x_src[q] . U_e^T); y[q] = u16[q] . D_e^T
+  if (run_grouped(GroupedOp{gb, p.x16, ws.kp, p.src, gate_epi(epi), p.t16, nullptr, nullptr}, g, p, st, nullptr) ||
+      run_grouped(GroupedOp{ub, p.x16, ws.kp, p.src, kEpiSiluMul, p.u16, p.t16, nullptr}, g, p, st, nullptr) ||
+      run_grouped(GroupedOp{db, p.u16, fmid, nullptr, kEpiNone, nullptr, nullptr, p.y}, g, p, st, nullptr))
+    return -1;
+  // launch 6: out[r] = sum_i w[r][i] * y[inv[r * top_k + i]], in slot order
+  const MoeGatherArgs c{p.y, fout, p.inv, wts, wts_ld, top_k, out, ldo, m, fout};
+  return launch(false, "moe gather kernel", [&] { return launch_moe_gather(c, st); }) ? 0 : -1;
+}
+
+extern "C" int nad_device_mul_mat_id_grouped(const void* bank, const float* act, const int32_t* ids, int ids_ld,
+                                             int slot, void* workspace, float* out, int m, int lda, int ldo,
+                                             void* queue) {
+  const char* who = "nad_device_mul_mat_id_grouped";
+  const NadExpertBank* b = as_bank(bank, who, "given");
+  if (!b) return -1;
+  if (!act || !ids || !out || !workspace || m < 0 || slot < 0 || slot >= ids_ld || ldo < b->w0.n ||
+      reinterpret_cast<uintptr_t>(workspace) % 16 != 0) {
+    set_err("%s: bad arguments (m=%d slot=%d ids_ld=%d ldo=%d n=%d; the workspace 16-B aligned)", who, m, slot, ids_ld,
+            ldo, b->w0.n);
+    return -1;
+  }
+  if (!grouped_bank_ok(*b, who, "given")) return -1;
+  const GroupedWs ws = grouped_ws(*b, nullptr, std::max(m, 1), 1);
+  GroupedGeom g;
+  if (!grouped_geometry(g, *b, &b, 1, std::max(m, 1), 1, ws, who)) return -1;
+  if (!rows_ok(act, lda, b->w0.k, who) || !launchable(*b, who)) return -1;
+  if (m == 0) return 0;
+  hipStream_t st = static_cast<hipStream_t>(queue);
+  const GroupedPtrs p = grouped_ptrs(workspace, ws);
+  const MoeSortArgs sa{ids + slot, ids_ld, m, 1, b->n_expert, g.bm, p.offs, p.perm, p.src, p.inv, p.tiles, p.ntiles};
+  if (!launch(false, "moe sort kernel", [&] { return launch_moe_sort(sa, st); })) return -1;
+  if (!launch(false, "activation conversion",
+              [&] { return launch_cvt_act(act, kActF32, lda, m, b->w0.k, ws.kp, nullptr, p.x16, st); }))
+    return -1;
+  if (run_grouped(GroupedOp{b, p.x16, ws.kp, p.src, kEpiNone, nullptr, nullptr, p.y}, g, p, st, nullptr)) return -1;
+  const MoeGatherArgs c{p.y, b->w0.n, p.inv, nullptr, 0, 1, out, ldo, m, b->w0.n};
+  return launch(false, "moe gather kernel", [&] { return launch_moe_gather(c, st); }) ? 0 : -1;
+}
+
+extern "C" int nad_plan_moe_grouped(const void* gate_bank, const void* up_bank, const void* down_bank, int m, int top_k,
+                                    int64_t* out, int nout) {
+  const char* who = "nad_plan_moe_grouped";
+  const NadExpertBank* gb = as_bank(gate_bank, who, "gate");
+  if (!gb) return -1;
+  const bool ffn = up_bank || down_bank;
+  const NadExpertBank* ub = ffn ? as_bank(up_bank, who, "up") : nullptr;
+  const NadExpertBank* db = ub ? as_bank(down_bank, who, "down") : nullptr;
+  if (ffn && !db) return -1;
+  if (!out || nout < 0 || m <= 0 || top_k <= 0 || (!ffn && top_k != 1)) {
+    set_err("%s: bad arguments (m=%d top_k=%d; the one-matmul form has top_k = 1)", who, m, top_k);
+    return -1;
+  }
+  GroupedWs ws;
+  GroupedGeom g;
+  if (ffn) {
+    if (!grouped_ffn_ok(*gb, *ub, *db, m, top_k, ws, g, who)) return -1;
+  } else {
+    if (!grouped_bank_ok(*gb, who, "given")) return -1;
+    ws = grouped_ws(*gb, nullptr, m, 1);
+    if (!grouped_geometry(g, *gb, &gb, 1, m, 1, ws, who)) return -1;
+  }
+  const GroupedPtrs p{};
+  int64_t v[27] = {};
+  int n = 0;
+  auto rec = [&](int64_t k, int64_t grid, int64_t threads) {
+    v[n] = k;
+    v[n + 1] = grid;
+    v[n + 2] = threads;
+    v[n + 3] = 0;
+    n += 4;
+  };
+  const int fout = ffn ? db->w0.n : gb->w0.n;
+  rec(NAD_KERNEL_MOE_SORT, 1, 1024);
+  rec(NAD_KERNEL_CVT_ACT, std::min<int64_t>((int64_t(m) * (ws.kp / 8) + 255) / 256, 4096), 256);
+  if (ffn) {
+    run_grouped(GroupedOp{gb, nullptr, 0, nullptr, kEpiSilu, nullptr, nullptr, nullptr}, g, p, nullptr, v + n);
+    n += 4;
+    run_grouped(GroupedOp{ub, nullptr, 0, nullptr, kEpiSiluMul, nullptr, nullptr, nullptr}, g, p, nullptr, v + n);
+    n += 4;
+    run_grouped(GroupedOp{db, nullptr, 0, nullptr, kEpiNone, nullptr, nullptr, nullptr}, g, p, nullptr, v + n);
+    n += 4;
+  } else {
+    run_grouped(GroupedOp{gb, nullptr, 0, nullptr, kEpiNone, nullptr, nullptr, nullptr}, g, p, nullptr, v + n);
+    n += 4;
+  }
+  rec(NAD_KERNEL_MOE_GATHER, int64_t((fout + 255) / 256) * m, 256);
+  const int launches = n / 4;
+  v[n++] = g.bm;
+  v[n++] = g.bound;
+  v[n++] = launches;
+  const int c = std::min(nout, n);
   std::memcpy(out, v, sizeof(int64_t) * size_t(c));
   return c;
 }

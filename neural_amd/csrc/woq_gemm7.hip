@@ -101,8 +101,20 @@ __device__ __forceinline__ h8_t dequant2_fold(uint32_t x, const Dq2c& q, h2_t sc
 // MW: several weights in one launch (fused QKV prefill, GemmArgs::nwt; int4 groups of 128 * 2^j, whole K) -- a
 // separate instantiation, so the single-weight kernel keeps its code (the runtime selection in it cost 2-4 %,
 // profiles/r06_gemm7_fused_qkv_ab.txt)
+#ifdef G7_GROUPED
+// The grouped form (objects of their own: woq_gemm7_g4.o / _g2.o, G7_GROUPED; the default compilation does not see
+// it): the same body for the sorted rows of routed experts (nad_device_moe_ffn_grouped).  Workgroup -> (tile, column
+// tile); the tile's expert and sorted row range [q0, q1) come from the device tile table the sort wrote, the weight
+// from the bank's entry of that expert, and the A rows through an optional index array (the activation row of a sorted
+// row: aoff[] is a per-lane source offset anyway, so the LDS-DMA gathers).  Whole K, one weight.
+template <int BITS, int BMT, bool ASYM, int ST, int GPT>
+__global__ __launch_bounds__(512, 1) void woq_gemm7_grouped_kernel(GemmArgs a, const _Float16* __restrict__ A16,
+                                                                    int lda16, GemmGrouped gg) {
+  constexpr bool MW = false;
+#else
 template <int BITS, int BMT, bool ASYM, int ST, int GPT, bool MW = false>
 __global__ __launch_bounds__(512, 1) void woq_gemm7_kernel(GemmArgs a, const _Float16* __restrict__ A16, int lda16) {
+#endif
   using BB = Bbuf<BITS, GPT, ST, ASYM>;
   using G = Geo<BMT, BB>;
   constexpr int RF = G::RF, HF = G::HF, HBUF = G::HBUF, PA = G::PA, NA = G::NA, DA = G::DA, DB = G::DB, NBR = G::NBR;
@@ -113,11 +125,36 @@ __global__ __launch_bounds__(512, 1) void woq_gemm7_kernel(GemmArgs a, const _Fl
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6));
   const int wn = wave & 3, wk = wave >> 2;
+#ifdef G7_GROUPED
+  const int nt = a.w.nt, ng = a.w.ng;
+#else
   const int M = a.M, nt = a.w.nt, ng = a.w.ng;  // the K side: shared by fused weights
+#endif
   // tile mode: K tiles per group (2^tsh); half-step mode: half steps per group (2^tsh, groups of 64 up)
   const int tpg = HS ? (a.w.bs >= 64 ? a.w.bs / 64 : 1) : (a.w.bs >= KT ? a.w.bs / KT : 1);
   const int tsh = __builtin_ctz(unsigned(tpg));
 
+#ifdef G7_GROUPED
+  // consecutive workgroups (one per XCD in turn) take the column tiles of one tile: column tile bn of every tile of an
+  // expert runs on XCD bn % 8 and finds that expert's B columns in its L2.  A workgroup past the device tile count
+  // leaves here, before any barrier.
+  const int nbn = (a.w.ns + NS - 1) / NS;
+  constexpr int nsplit = 1, ks = 0, kt0 = 0;
+  const int tile = int(blockIdx.x) / nbn, bn = int(blockIdx.x) - tile * nbn;
+  if (tile >= __builtin_amdgcn_readfirstlane(*gg.ntiles)) return;
+  const int4 te = gg.tiles[tile];  // (expert, q0, q1, 0): q0 < q1 <= q0 + BMT, expert < n_expert (the sort's contract)
+  const int m0 = __builtin_amdgcn_readfirstlane(te.y), M = __builtin_amdgcn_readfirstlane(te.z);
+  const GemvExpertEnt ge = gg.bank[__builtin_amdgcn_readfirstlane(te.x)];
+  SkinnyWeight Wg = a.w;
+  Wg.tiles = ge.tiles;
+  Wg.scales = ge.scales;
+  Wg.zps = ge.zps;
+  const SkinnyWeight& W = Wg;
+  const int ntl = nt;
+  const int nh = HPT * ntl;
+  const int nh2 = (nh + 1) & ~1;
+  const int ns = W.ns;
+#else
   // XCD-aware remap (one XCD walks the N tiles of one (M tile, K run)) and split-K runs, as gemm3
   const int nbm = (M + BMT - 1) / BMT;
   const int nbn = MW ? a.nbn_all : (a.w.ns + NS - 1) / NS;
@@ -146,6 +183,7 @@ __global__ __launch_bounds__(512, 1) void woq_gemm7_kernel(GemmArgs a, const _Fl
   const SkinnyWeight& W = MW && wi != 0 ? a.wf[wi - 1] : a.w;
   const int ns = W.ns;
   const int m0 = bm * BMT;
+#endif
   const int nl = lane & 15, kq = lane >> 4;
 
   // A piece p: rows 8p .. 8p + 7, lane -> row 8p + (lane >> 3), chunk (lane & 7) ^ ((row >> 1) & 7)
@@ -155,7 +193,12 @@ __global__ __launch_bounds__(512, 1) void woq_gemm7_kernel(GemmArgs a, const _Fl
   for (int i = 0; i < PA; i++) {
     const int p = (wave * PA + i) % G::PIECES;
     const int row = p * 8 + (lane >> 3);
+#ifdef G7_GROUPED
+    const int srow = min(m0 + row, M - 1);  // rows past q1 re-read the tile's last row (never stored)
+    const int grow = gg.rows ? gg.rows[srow] : srow;
+#else
     const int grow = min(m0 + row, M - 1);  // rows past M re-read row M - 1 (never stored)
+#endif
     aoff[i] = uint32_t(grow) * uint32_t(lda16) * 2u + uint32_t(((lane & 7) ^ ((row >> 1) & 7)) * 16);
     adst[i] = smem + p * 1024;
   }
@@ -458,6 +501,7 @@ __global__ __launch_bounds__(512, 1) void woq_gemm7_kernel(GemmArgs a, const _Fl
 #define G7_CAT2(x, y) x##y
 #define G7_CAT(x, y) G7_CAT2(x, y)
 
+#ifndef G7_GROUPED
 hipError_t G7_CAT(launch_gemm7_b, G7_BITS)(const GemmArgs& a, int bm, const _Float16* A16, int lda16, hipStream_t st) {
   constexpr int BITS = G7_BITS;
   const int nbm = (a.M + bm - 1) / bm, nbn = a.nwt > 1 ? a.nbn_all : (a.w.ns + g7::NS - 1) / g7::NS;
@@ -528,5 +572,70 @@ hipError_t launch_gemm7(const GemmArgs& a, int bits, int bm, const _Float16* A16
                      : launch_gemm7_b4(a, bm, A16, lda16, st);
 }
 #endif
+
+#else  // G7_GROUPED: woq_gemm7_g4.o (int4), woq_gemm7_g2.o (int2) hold the grouped kernel and its launcher only
+// grid: column tiles x the host's tile bound (the device tile count decides which workgroups work).  lds_out set: no
+// launch, *lds_out = the dynamic LDS of the instantiation that would serve it (nad_plan_moe_grouped).
+hipError_t G7_CAT(launch_gemm7_grouped_b, G7_BITS)(const GemmArgs& a, const GemmGrouped& gg, int bm, int grid,
+                                                   const _Float16* A16, int lda16, hipStream_t st, int* lds_out) {
+  constexpr int BITS = G7_BITS;
+  static_assert(BITS == 4 || BITS == 2, "banks hold int4 / int2");
+  const int gpt = BITS == 4 ? (a.w.bs == 32 ? 4 : (a.w.bs == 64 ? 2 : 1)) : (a.w.bs == 32 ? 2 : 1);
+  auto pick = [&](auto bmc) -> hipError_t {
+    constexpr int BMT = decltype(bmc)::value;
+    auto sel = [&](auto asc, auto stc, auto gc) -> hipError_t {
+      constexpr bool AS = decltype(asc)::value;
+      constexpr int STT = decltype(stc)::value, GP = decltype(gc)::value;
+      constexpr int LDS = g7::Geo<BMT, g7::Bbuf<BITS, GP, STT, AS>>::LDS;
+      if (lds_out) {
+        *lds_out = LDS;
+        return hipSuccess;
+      }
+      return launch_big_lds<g7::woq_gemm7_grouped_kernel<BITS, BMT, AS, STT, GP>>(dim3(grid), dim3(512), LDS, st, a, A16,
+                                                                                  lda16, gg);
+    };
+    // what an expert bank can hold (nad_expert_bank_create takes the M = 1 GEMV's geometries): int4 groups of 64 (two
+    // per K tile) and 128 * 2^j, int2 groups of 64 * 2^j -- groups of 32 have no bank, so no instantiation here
+    auto by_gpt = [&](auto asc, auto stc) -> hipError_t {
+      if constexpr (BITS == 4) {
+        if (gpt == 2) return sel(asc, stc, std::integral_constant<int, 2>{});
+      }
+      return gpt == 1 ? sel(asc, stc, std::integral_constant<int, 1>{}) : hipErrorInvalidValue;
+    };
+    auto by_st = [&](auto asc) {
+      switch (a.scale_t) {
+        case kScaleF32:
+          return by_gpt(asc, std::integral_constant<int, kScaleF32>{});
+        case kScaleBF16:
+          return by_gpt(asc, std::integral_constant<int, kScaleBF16>{});
+        default:
+          return by_gpt(asc, std::integral_constant<int, kScaleF16>{});
+      }
+    };
+    return a.w.zps != nullptr ? by_st(std::true_type{}) : by_st(std::false_type{});
+  };
+  switch (bm) {
+    case 32:
+      return pick(std::integral_constant<int, 32>{});
+    case 64:
+      return pick(std::integral_constant<int, 64>{});
+    case 128:
+      return pick(std::integral_constant<int, 128>{});
+    default:
+      return pick(std::integral_constant<int, 256>{});
+  }
+}
+
+#if G7_BITS == 4
+hipError_t launch_gemm7_grouped_b2(const GemmArgs& a, const GemmGrouped& gg, int bm, int grid, const _Float16* A16,
+                                   int lda16, hipStream_t st, int* lds_out);
+
+hipError_t launch_gemm7_grouped(const GemmArgs& a, const GemmGrouped& gg, int bits, int bm, int grid,
+                                const _Float16* A16, int lda16, hipStream_t st, int* lds_out) {
+  return bits == 2 ? launch_gemm7_grouped_b2(a, gg, bm, grid, A16, lda16, st, lds_out)
+                   : launch_gemm7_grouped_b4(a, gg, bm, grid, A16, lda16, st, lds_out);
+}
+#endif
+#endif  // G7_GROUPED
 
 }  // namespace nad

@@ -192,6 +192,49 @@ struct MoeRouteArgs {
 };
 hipError_t launch_moe_route(const MoeRouteArgs& a, hipStream_t stream);
 
+// Sorted, grouped expert GEMMs (nad_device_moe_ffn_grouped / nad_device_mul_mat_id_grouped).  Problem p = r * top_k + i
+// has expert ids[r * ids_ld + i] and is valid when that lies in [0, n_expert).  moe_sort_kernel, one workgroup, writes
+// from ids alone (a stable counting sort: ballots and prefix sums, no atomics, so the bytes are a function of ids):
+//   offs[0 .. n_expert]  expert e owns the sorted rows offs[e] .. offs[e + 1] - 1; offs[n_expert] = the valid problems
+//   perm[q]              the valid problems ordered by (expert, p); -1 from offs[n_expert] on
+//   src[q]               perm[q] / top_k, the activation row of sorted row q; 0 from offs[n_expert] on
+//   inv[p]               the sorted position of p, -1 for an invalid id
+//   tiles[t]             (expert, q0, q1, 0) in expert order, ceil(count_e / bm) per expert, q1 - q0 <= bm
+//   ntiles[0]            the tile count, at most np / bm + min(n_expert, np)
+struct MoeSortArgs {
+  const int32_t* ids;
+  int ids_ld, m, top_k, n_expert, bm;
+  int32_t *offs, *perm, *src, *inv;
+  int4* tiles;
+  int32_t* ntiles;
+};
+hipError_t launch_moe_sort(const MoeSortArgs& a, hipStream_t stream);
+// What woq_gemm7_grouped_kernel takes beside the GemmArgs of one expert's GEMM (a.w: the bank's shape and format, its
+// pointers unused; a.M unused; whole K)
+struct GemmGrouped {
+  const GemvExpertEnt* bank;  // [n_expert]
+  const int4* tiles;          // MoeSortArgs::tiles
+  const int32_t* ntiles;
+  const int32_t* rows;        // A row of sorted row q (MoeSortArgs::src), or null: A holds the sorted rows themselves
+};
+// bits 4 / 2, bm 32 / 64 / 128 / 256 (anything else: 256), grid = tile bound * ceil(ns / 8).  lds_out set: no launch,
+// *lds_out = the dynamic LDS bytes of the instantiation that would serve it.
+hipError_t launch_gemm7_grouped(const GemmArgs& a, const GemmGrouped& g, int bits, int bm, int grid, const _Float16* A16,
+                                int lda16, hipStream_t stream, int* lds_out);
+// out[r][n] = ((w[r][0] * y[inv[r * top_k]][n]) + w[r][1] * y[inv[r * top_k + 1]][n]) + ... with moe_combine_kernel's
+// arithmetic; a slot with inv < 0 contributes w * 0.0f.  wts null (top_k = 1): out[r] = y[inv[r]], or zeros.
+struct MoeGatherArgs {
+  const float* y;  // [valid problems][ldy], sorted rows
+  int ldy;
+  const int32_t* inv;
+  const float* wts;
+  int wts_ld;
+  int top_k;
+  float* out;
+  int ldo, m, n;
+};
+hipError_t launch_moe_gather(const MoeGatherArgs& a, hipStream_t stream);
+
 // The arguments of woq_gemv_m1s_kernel: only what that kernel reads, with everything that is constant per launch
 // worked out by launch_gemv (K-slices per stripe, units per workgroup).  NWS: weights in the launch (1; 3 = fused QKV;
 // 2 = the {gate, up} pair of the SiLU*mul epilogue).

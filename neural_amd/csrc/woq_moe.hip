@@ -1,6 +1,7 @@
 // woq_moe.hip -- the two small kernels around the routed expert matmuls (woq_gemv_m1_routed_kernel, woq_gemv.hip) of a
 // Mixtral-style FFN (models/llama/llama.cpp:620-688): the router (softmax -> top_k -> renormalise, :624-638) and the
-// weighted sum of the slot results (ne_mul then ne_add per slot, :676-679).
+// weighted sum of the slot results (ne_mul then ne_add per slot, :676-679); and around the sorted, grouped form
+// (woq_gemm7_grouped_kernel, woq_gemm7.hip): the sort of the problems by expert and the same sum over sorted rows.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -75,6 +76,161 @@ __global__ __launch_bounds__(64) void moe_route_kernel(MoeRouteArgs a) {
 
 hipError_t launch_moe_route(const MoeRouteArgs& a, hipStream_t stream) {
   hipLaunchKernelGGL(moe_route_kernel, dim3(a.m), dim3(64), 0, stream, a);
+  return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------ grouped: the sort
+// The stable counting sort of the problems by expert (MoeSortArgs, woq_kernels.h), one workgroup of 16 waves.  Wave w
+// owns the contiguous problems [w * seg, (w + 1) * seg) and walks them 64 at a time, twice:
+//   1. cnt[w][e] = its problems of expert e.  The lanes of one expert in a block of 64 are found by ballot, one expert
+//      per round (as many rounds as the block has experts), and counted by popcount.
+//   2. wave 0 scans the totals: offs[] and the first tile of every expert; cnt[w][e] becomes the exclusive sum over the
+//      waves, i.e. how many problems of e lie before wave w's.
+//   3. the same walk again: problem p of expert e in lane l goes to offs[e] + cnt[w][e] + (lanes of e below l), then
+//      cnt[w][e] moves on by the block's count.
+// Every position is a sum of counts of problems before p: no atomic decides anything, two runs write the same bytes.
+constexpr int kSortWaves = 16, kSortMaxE = 256;
+
+__global__ __launch_bounds__(kSortWaves * 64) void moe_sort_kernel(MoeSortArgs a) {
+  __shared__ int cnt[kSortWaves][kSortMaxE];
+  __shared__ int tot[kSortMaxE], offs_s[kSortMaxE + 1], tb[kSortMaxE + 1];
+  const int tid = int(threadIdx.x), lane = tid & 63, wave = tid >> 6;
+  const int ne = a.n_expert, np = a.m * a.top_k;
+  const int seg = (np + kSortWaves * 64 - 1) / (kSortWaves * 64) * 64;
+  const int p0 = min(np, wave * seg), p1 = min(np, p0 + seg);
+  for (int i = tid; i < kSortWaves * kSortMaxE; i += kSortWaves * 64) (&cnt[0][0])[i] = 0;
+  __syncthreads();
+
+  // one block of 64 problems: fn(expert, the lanes of that expert) once per expert present, in lane order of the
+  // expert's first problem; returns this lane's id
+  auto block = [&](int b, auto&& fn) {
+    const int p = b + lane;
+    int e = -1;
+    if (p < p1) {
+      const int r = p / a.top_k;
+      e = a.ids[size_t(r) * a.ids_ld + (p - r * a.top_k)];
+    }
+    const bool valid = unsigned(e) < unsigned(ne);
+    unsigned long long todo = __ballot(valid);
+    while (todo) {
+      const int ef = __builtin_amdgcn_readfirstlane(__shfl(e, __ffsll(todo) - 1, 64));
+      const unsigned long long mk = __ballot(valid && e == ef);
+      fn(ef, mk, valid && e == ef, p);
+      todo &= ~mk;
+    }
+    return valid;
+  };
+
+  for (int b = p0; b < p1; b += 64)
+    block(b, [&](int ef, unsigned long long mk, bool, int) {
+      if (lane == 0) cnt[wave][ef] += __popcll(mk);
+    });
+  __syncthreads();
+
+  if (tid < ne) {
+    int s = 0;
+    for (int w = 0; w < kSortWaves; w++) {
+      const int c = cnt[w][tid];
+      cnt[w][tid] = s;
+      s += c;
+    }
+    tot[tid] = s;
+  }
+  __syncthreads();
+  if (wave == 0) {  // lane l: experts 4 l .. 4 l + 3
+    int c[4], sc = 0, st = 0;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      c[j] = lane * 4 + j < ne ? tot[lane * 4 + j] : 0;
+      sc += c[j];
+      st += (c[j] + a.bm - 1) / a.bm;
+    }
+    int ic = sc, it = st;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int uc = __shfl_up(ic, o, 64), ut = __shfl_up(it, o, 64);
+      if (lane >= o) {
+        ic += uc;
+        it += ut;
+      }
+    }
+    int rc = ic - sc, rt = it - st;
+    if (lane == 0) offs_s[0] = tb[0] = 0;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      rc += c[j];
+      rt += (c[j] + a.bm - 1) / a.bm;
+      if (lane * 4 + j < ne) {
+        offs_s[lane * 4 + j + 1] = rc;
+        tb[lane * 4 + j + 1] = rt;
+      }
+    }
+  }
+  __syncthreads();
+
+  const int nvalid = offs_s[ne], ntiles = tb[ne];
+  if (tid <= ne) a.offs[tid] = offs_s[tid];
+  if (tid == 0) a.ntiles[0] = ntiles;
+  for (int t = tid; t < ntiles; t += kSortWaves * 64) {
+    int lo = 0, hi = ne;  // the expert with tb[e] <= t < tb[e + 1]
+    while (hi - lo > 1) {
+      const int mid = (lo + hi) >> 1;
+      if (tb[mid] <= t) lo = mid; else hi = mid;
+    }
+    const int q0 = offs_s[lo] + (t - tb[lo]) * a.bm;
+    a.tiles[t] = make_int4(lo, q0, min(q0 + a.bm, offs_s[lo + 1]), 0);
+  }
+  for (int q = nvalid + tid; q < np; q += kSortWaves * 64) {
+    a.perm[q] = -1;
+    a.src[q] = 0;
+  }
+
+  for (int b = p0; b < p1; b += 64) {
+    const bool valid = block(b, [&](int ef, unsigned long long mk, bool mine, int p) {
+      const int base = offs_s[ef] + cnt[wave][ef];
+      if (mine) {
+        const int q = base + __popcll(mk & ((1ull << lane) - 1ull));
+        a.perm[q] = p;
+        a.src[q] = p / a.top_k;
+        a.inv[p] = q;
+      }
+      if (lane == 0) cnt[wave][ef] = base - offs_s[ef] + __popcll(mk);
+    });
+    if (!valid && b + lane < p1) a.inv[b + lane] = -1;
+  }
+}
+
+hipError_t launch_moe_sort(const MoeSortArgs& a, hipStream_t stream) {
+  if (a.n_expert < 1 || a.n_expert > kSortMaxE || a.bm < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(moe_sort_kernel, dim3(1), dim3(kSortWaves * 64), 0, stream, a);
+  return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------ grouped: the way back
+// moe_combine_kernel's sum over the sorted rows (MoeGatherArgs): slot i of row r lies at y[inv[r * top_k + i]], an
+// invalid slot reads 0.0f
+__global__ __launch_bounds__(256) void moe_gather_kernel(MoeGatherArgs a) {
+  const int nb = (a.n + 255) / 256, r = int(blockIdx.x) / nb;
+  const int n = (int(blockIdx.x) - r * nb) * 256 + int(threadIdx.x);
+  if (n >= a.n) return;
+  const int32_t* inv = a.inv + size_t(r) * a.top_k;
+  auto y = [&](int i) {
+    const int q = inv[i];
+    return q >= 0 ? a.y[size_t(q) * a.ldy + n] : 0.0f;
+  };
+  float s;
+  if (a.wts) {
+    const float* w = a.wts + size_t(r) * a.wts_ld;
+    s = w[0] * y(0);
+    for (int i = 1; i < a.top_k; i++) s = s + w[i] * y(i);
+  } else {
+    s = y(0);
+  }
+  a.out[size_t(r) * a.ldo + n] = s;
+}
+
+hipError_t launch_moe_gather(const MoeGatherArgs& a, hipStream_t stream) {
+  hipLaunchKernelGGL(moe_gather_kernel, dim3(unsigned((a.n + 255) / 256) * unsigned(a.m)), dim3(256), 0, stream, a);
   return hipGetLastError();
 }
 

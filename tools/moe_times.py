@@ -16,6 +16,18 @@ Bytes: per (row, slot) the three weights' device bytes (tiles + scales), the act
 the time, as a fraction of 8 TB/s.
 
 Usage: python tools/moe_times.py [--rounds 5] [--replays 200] [--out FILE]
+
+--grouped: the same layer at batched-decode and prefill sizes (M = 8, 16, 64, 256, 2048; a random top-2 routing, experts
+distinct per row), three ways, alternating in one process, graph replay, HIP events:
+
+  (a) bestla.moe_ffn_grouped: sorted on the device, grouped gemm7, six launches;
+  (b) bestla.moe_ffn: the row-routed form, every problem streaming its expert's weights (few replays where M is large);
+  (c) what the library could do without either, given the ids on the host already: the rows gathered into expert order
+      (index_select), one bestla.ffn_forward per expert on its contiguous rows, and the weighted sum over the slots
+      (index_select, multiply, sum).  As above this leaves out the ids' copy to the host and the synchronisation.
+
+A graph holds one call on each of two layers' banks (one layer's experts are 0.7 GB int4: more than the Infinity Cache
+on their own).  A window replays the graph until it has run about --window-ms.
 """
 import argparse
 import math
@@ -34,13 +46,143 @@ FORMATS = {
 }
 
 
+def grouped(args):
+    import torch
+    from neural_amd import bestla
+
+    lines = []
+
+    def say(s):
+        print(s, flush=True)
+        lines.append(s)
+
+    say(f"{torch.cuda.get_device_name()}  Mixtral-8x7B FFN layer, fin {FIN} fmid {FMID} fout {FOUT}, {NE} experts, "
+        f"top-{TOP_K}, fp32 rows, random routing")
+    say(f"us per layer call: median of {args.rounds} alternating rounds (min .. max); a graph of 2 layer calls replayed "
+        f"for about {args.window_ms} ms per window")
+    say(f"{'format':<36}{'M':>5} {'bm':>4}  {'(a) moe_ffn_grouped us':>30}  {'(b) moe_ffn us':>32}  "
+        f"{'(c) per-expert ffn_forward us':>32}  {'a/b':>6}  {'a/c':>6}  {'(a) TFLOP/s':>11}  {'a-b diff':>9}  {'a-c diff':>9}")
+    L = 2
+    for name, ((gbits, ggs), (dbits, dgs)) in FORMATS.items():
+        def make(bits, n, k, gs, seed):
+            return bestla.DeviceWeight.synthetic(bits, n, k, gs, "fp16", False, seed=seed)
+
+        layers = []
+        for li in range(L):
+            g = [make(gbits, FMID, FIN, ggs, 1000 * li + e) for e in range(NE)]
+            u = [make(gbits, FMID, FIN, ggs, 1000 * li + 100 + e) for e in range(NE)]
+            d = [make(dbits, FOUT, FMID, dgs, 1000 * li + 200 + e) for e in range(NE)]
+            layers.append((g, u, d, bestla.ExpertBank(g), bestla.ExpertBank(u), bestla.ExpertBank(d)))
+        for m in (8, 16, 64, 256, 2048):
+            np_ = m * TOP_K
+            gen = torch.Generator(device="cuda").manual_seed(m)
+            x = torch.rand((m, FIN), device="cuda", generator=gen) - 0.5
+            ids = torch.rand((m, NE), device="cuda", generator=gen).topk(TOP_K, dim=1).indices.to(torch.int32)
+            w = torch.rand((m, TOP_K), device="cuda", generator=gen) + 0.1
+            w = (w / w.sum(dim=1, keepdim=True)).contiguous()
+            # (c)'s host-side routing, made once outside the timed region
+            flat = ids.flatten().cpu()
+            order = torch.sort(flat, stable=True).indices
+            counts = torch.bincount(flat, minlength=NE).tolist()
+            src = (order // TOP_K).cuda()
+            inv = torch.empty(np_, dtype=torch.int64)
+            inv[order] = torch.arange(np_)
+            inv = inv.cuda()
+            outs = {k: torch.empty((m, FOUT), device="cuda") for k in "abc"}
+            xs = torch.empty((np_, FIN), device="cuda")
+            ys = torch.empty((np_, FOUT), device="cuda")
+            yp = torch.empty((np_, FOUT), device="cuda")
+            tmp1 = torch.empty((np_, FMID), device="cuda")
+            tmp2 = torch.empty((np_, FMID), device="cuda")
+            gb0, ub0, db0 = layers[0][3:]
+            ws_a = bestla.moe_grouped_workspace_alloc(gb0, ub0, db0, m, TOP_K)
+            ws_b = bestla.moe_workspace_alloc(m, TOP_K, FMID, FOUT)
+
+            def run_a(j, s):
+                _, _, _, gb, ub, db = layers[j]
+                bestla.moe_ffn_grouped(gb, ub, db, x, ids, w, out=outs["a"], stream=s, workspace=ws_a)
+
+            def run_b(j, s):
+                _, _, _, gb, ub, db = layers[j]
+                bestla.moe_ffn(gb, ub, db, x, ids, w, out=outs["b"], stream=s, workspace=ws_b)
+
+            def run_c(j, s):
+                g, u, d, _, _, _ = layers[j]
+                torch.index_select(x, 0, src, out=xs)
+                o = 0
+                for e in range(NE):
+                    c = counts[e]
+                    if c:
+                        bestla.ffn_forward(xs[o:o + c], g[e], d[e], u[e], tmp1=tmp1[o:o + c], tmp2=tmp2[o:o + c],
+                                           out=ys[o:o + c], stream=s)
+                    o += c
+                torch.index_select(ys, 0, inv, out=yp)
+                torch.sum(yp.view(m, TOP_K, FOUT) * w[:, :, None], dim=1, out=outs["c"])
+
+            s = torch.cuda.Stream()
+            s.wait_stream(torch.cuda.current_stream())
+            graphs, replays, times = {}, {}, {k: [] for k in "abc"}
+            with torch.cuda.stream(s):
+                for key, fn in (("a", run_a), ("b", run_b), ("c", run_c)):
+                    for j in range(L):
+                        fn(j, s)
+                    gr = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(gr, stream=s):
+                        for j in range(L):
+                            fn(j, s)
+                    gr.replay()
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record(s)
+                    gr.replay()
+                    e1.record(s)
+                    e1.synchronize()
+                    graphs[key] = gr
+                    replays[key] = max(1, min(args.replays, int(args.window_ms / max(e0.elapsed_time(e1), 1e-3))))
+                s.synchronize()
+                scale = float(outs["a"].abs().max())
+                dab = float((outs["a"] - outs["b"]).abs().max()) / scale
+                dac = float((outs["a"] - outs["c"]).abs().max()) / scale
+                for _ in range(args.rounds):
+                    for key in "abc":
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        e0.record(s)
+                        for _ in range(replays[key]):
+                            graphs[key].replay()
+                        e1.record(s)
+                        e1.synchronize()
+                        times[key].append(e0.elapsed_time(e1) * 1e3 / (replays[key] * L))
+            torch.cuda.synchronize()
+            med = {k: statistics.median(v) for k, v in times.items()}
+            cell = {k: f"{med[k]:10.1f} ({min(v):.1f} .. {max(v):.1f})" for k, v in times.items()}
+            bm = bestla.plan_moe_grouped(gb0, ub0, db0, m, TOP_K)["bm"]
+            flops = 2.0 * np_ * (2 * FIN * FMID + FMID * FOUT)
+            say(f"{name:<36}{m:>5} {bm:>4}  {cell['a']:>30}  {cell['b']:>32}  {cell['c']:>32}  "
+                f"{med['a'] / med['b']:6.3f}  {med['a'] / med['c']:6.3f}  {flops / med['a'] * 1e-6:11.1f}  {dab:9.1e}  "
+                f"{dac:9.1e}")
+            del graphs
+        plan = bestla.plan_moe_grouped(layers[0][3], layers[0][4], layers[0][5], 2048, TOP_K)
+        say("  launches at M = 2048: " + ", ".join(f"{p['kernel']} grid {p['grid']} x {p['threads']}"
+                                                   for p in plan["launches"]) +
+            f"; tile height {plan['bm']}, tile bound {plan['bound']}")
+        del layers
+        torch.cuda.empty_cache()
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--grouped", action="store_true", help="M = 16 .. 2048: grouped vs row-routed vs per-expert calls")
+    ap.add_argument("--window-ms", type=float, default=60.0, help="--grouped: about this much work per timed window")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--replays", type=int, default=200, help="graph replays per timed window")
     ap.add_argument("--gib", type=float, default=1.0, help="distinct weight bytes a replay streams, at least")
     ap.add_argument("--out", default=None, help="also write the table here")
     args = ap.parse_args()
+    if args.grouped:
+        return grouped(args)
     import torch
     from neural_amd import bestla
 
