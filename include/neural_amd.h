@@ -156,6 +156,29 @@ void nad_clear_error(void);
 size_t nad_device_weight_size(const void* hostblob);
 /* bestla_device_load_storage with an explicit capacity check and a status return */
 int nad_device_load(const void* hostblob, void* devstor, void* deviceptr, size_t capacity, void* queue);
+/* ===== quantize and pack on the device: BTLAGemmQuantPackB + nad_device_load for a matrix that already sits in HBM,
+ * byte-identical to that host path.  Integer weights only: qtype S4_CLIP, S2_CLIP or S8, sym or asym, F32 / BF16 / F16
+ * scales, any CompType (the core is select_core's, so NAD_HOST_ISA picks the same one as on the host path), any group
+ * size nad_device_load takes (blocksize <= 0 or >= k: per-channel; a partial last group is fine).  S1 / S3 / S5..S7,
+ * F4 / F8 weights and DQ8_BNB / F8_E8M0 scales are refused by name: they stay on the host path.
+ *
+ * The arithmetic is quantize_kblock's sNauto branch operation for operation (fp16 / bf16 inputs are widened exactly;
+ * the float -> int cast gives INT_MIN for NaN as the x86 cast does, which is how an all-zero group gets code 0 (sym) or
+ * zero point 2^(bits-1) - 1 with codes -2^(bits-1) (asym)), so for every finite input the blob equals the host packer's
+ * byte for byte.  For non-finite inputs the codes are unspecified; nothing faults or reads outside [n][0:k]. */
+/* device bytes of the weight (== nad_device_weight_size of the blob BTLAGemmQuantPackB would write);
+ * *blob_size (may be NULL) = BTLAGemmPackBSize of the same arguments; 0 + nad_last_error on refusal */
+size_t nad_device_quantize_size(int n, int k, int blocksize, uint32_t qtype, uint32_t scale_dtype, int asym, int comp,
+                                size_t* blob_size);
+/* w: device [n][ldw] of w_dtype (the act dtype codes 0 fp32 / 1 fp16 / 2 bf16), ldw >= k.  Writes the descriptor and
+ * exactly the first `bytes` of deviceptr (what nad_device_load writes of them); if blob_out != NULL also the blob --
+ * header and every section, the padding of the sections as zeros -- into host memory (64-byte aligned blobs of the two
+ * paths compare equal when both buffers were zero-filled: the serializer aligns relative to the base).  Errors (a null
+ * pointer, ldw < k, a capacity too small -- the message states the need --, a refused dtype) are found before any
+ * device work.  Synchronous, allocates its staging and frees it, like nad_device_load; not for graph capture. */
+int nad_device_quantize(const void* w, int w_dtype, int n, int k, int ldw, int blocksize, uint32_t qtype,
+                        uint32_t scale_dtype, int asym, int comp, void* devstor, void* deviceptr, size_t capacity,
+                        void* blob_out, size_t blob_capacity, void* queue);
 /* descriptor summary: [magic, bits, n, k, blocksize, ns, nt, ng, scale_t, asym, has_shuffle, bytes] */
 int nad_weight_info(const void* devstor, int64_t* out12);
 /* the same, versioned by the caller's buffer: writes min(n, 13) values ([12] = fold_ok: every q * scale is an fp16

@@ -63,6 +63,8 @@ SIGNATURES = {
     "nad_clear_error": (None, []),
     "nad_device_weight_size": (_sz, [_p]),
     "nad_device_load": (_i, [_p, _p, _p, _sz, _p]),
+    "nad_device_quantize_size": (_sz, [_i, _i, _i, _u32, _u32, _i, _i, _p]),
+    "nad_device_quantize": (_i, [_p, _i, _i, _i, _i, _i, _u32, _u32, _i, _i, _p, _p, _sz, _p, _sz, _p]),
     "nad_weight_info": (_i, [_p, _p]),
     "nad_weight_info2": (_i, [_p, _p, _i]),
     "nad_reload_knobs": (None, []),

@@ -74,9 +74,8 @@ def pack_size(n, k, block_size, weight_dtype=S4, scale_dtype=F32, asym=False, co
                                C.byref(dummy) if shuffle else None)
 
 
-def quantize(w_nk, group_size=32, weight_dtype="int4", scale_dtype="fp32", alg="sym", compute_dtype="int8"):
-    """bestla_quantize (quant_utils.cpp:269-354): fp32 torch-layout weight [N][K] -> packed BTLA blob (uint8)."""
-    w = np.ascontiguousarray(w_nk, dtype=np.float32)
+def _quantize_types(weight_dtype, scale_dtype):
+    """The BTLA_DTYPE codes bestla_quantize packs with for these names (weight, scale)."""
     qt = parse_weight_dtype(weight_dtype)
     if scale_dtype not in _SCALE_DTYPES:
         raise ValueError(f"unsupported scale_dtype {scale_dtype!r} (supported: {sorted(_SCALE_DTYPES)})")
@@ -85,6 +84,13 @@ def quantize(w_nk, group_size=32, weight_dtype="int4", scale_dtype="fp32", alg="
         st = F8_E8M0  # quant_utils.cpp:336-341: fp8 weights always get F8_E8M0 shared-exponent scales
     elif st == F8_E8M0:
         st = BF16  # quant_utils.cpp:329-335: anything but fp32 / fp16 is stored as bf16
+    return qt, st
+
+
+def quantize(w_nk, group_size=32, weight_dtype="int4", scale_dtype="fp32", alg="sym", compute_dtype="int8"):
+    """bestla_quantize (quant_utils.cpp:269-354): fp32 torch-layout weight [N][K] -> packed BTLA blob (uint8)."""
+    w = np.ascontiguousarray(w_nk, dtype=np.float32)
+    qt, st = _quantize_types(weight_dtype, scale_dtype)
     gsize = w.shape[1] if group_size == -1 else group_size
     return quant_pack(w, gsize, qt, st, alg == "asym", _COMP[compute_dtype])
 
@@ -329,6 +335,36 @@ class DeviceWeight:
         desc = (C.c_uint8 * L.bestla_device_storage_size())()
         check(L.nad_q6_k_device_load(_ptr(blocks), n, k, desc, _ptr(mem), need, _stream(stream)), "nad_q6_k_device_load")
         return cls(_desc=desc, _mem=mem)
+
+    @classmethod
+    def quantize(cls, w, group_size=32, weight_dtype="int4", scale_dtype="fp32", alg="sym", compute_dtype="int8",
+                 return_blob=False, stream=None):
+        """bestla.quantize + DeviceWeight for a weight that already sits in HBM (nad_device_quantize): w is a cuda
+        tensor [N][K] fp32 / fp16 / bf16 with K contiguous (a row stride is honoured), quantized, packed and laid out by
+        HIP kernels, byte-identical to the host path.  int4 / int2 / int8 weights with fp32 / bf16 / fp16 scales;
+        anything else raises and stays on the host path.  Returns the DeviceWeight, or (DeviceWeight, blob) with the
+        blob bestla.quantize would return when return_blob is true."""
+        torch = _torch()
+        L = lib()
+        if w.dim() != 2 or not w.is_cuda or w.stride(1) != 1:
+            raise ValueError("DeviceWeight.quantize takes a cuda tensor [N][K] with K contiguous")
+        n, k = w.shape
+        qt, st = _quantize_types(weight_dtype, scale_dtype)
+        gsize = k if group_size == -1 else group_size
+        asym, comp = int(alg == "asym"), _COMP[compute_dtype]
+        bsz = C.c_size_t(0)
+        need = L.nad_device_quantize_size(n, k, gsize, qt, st, asym, comp, C.byref(bsz))
+        if not need:
+            raise RuntimeError(f"nad_device_quantize_size failed: {last_error()}")
+        blob = _aligned_buffer(bsz.value) if return_blob else None
+        mem = torch.empty(need, dtype=torch.uint8, device=w.device)
+        desc = (C.c_uint8 * L.bestla_device_storage_size())()
+        with torch.cuda.device(w.device):
+            check(L.nad_device_quantize(_ptr(w), _act_code(w), n, k, w.stride(0), gsize, qt, st, asym, comp, desc,
+                                        _ptr(mem), need, _ptr(blob), bsz.value if return_blob else 0, _stream(stream)),
+                  "nad_device_quantize")
+        dw = cls(_desc=desc, _mem=mem)
+        return (dw, blob) if return_blob else dw
 
     def forward(self, x, out=None, epilogue=EPI_NONE, bias=None, residual=None, stream=None):
         """out[m][n] = epi(sum_k x[m][k] * W[n][k]); x: cuda [M][K] fp32/fp16/bf16 (row stride honoured)."""

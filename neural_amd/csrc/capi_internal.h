@@ -99,6 +99,13 @@ bool q8k_compute(const nad::DeviceWeight& w);   // a Q6_K weight set to NAD_COMP
 // base: the host blob, scanned for codes the device cannot hold (load time only; null skips the scan)
 bool blob_supported(const nad::Blob& b, const void* base, std::string* err);
 inline bool blob_supported(const nad::Blob& b, std::string* err) { return blob_supported(b, nullptr, err); }
+// for capi_quant.hip, which fills a descriptor the way nad_device_load does: the ScaleType of a blob scale dtype, the
+// fold_ok rule over the scales at base + b.s_off, and the repack of the blob's sections once they are on the device
+// (dz null: symmetric)
+int scale_code(uint32_t scale_dtype);
+bool blob_fold_ok(const nad::Blob& b, const uint8_t* base, int dev_bits);
+int repack_sections(const nad::Blob& b, const nad::DeviceWeight& w, const uint8_t* dq, const void* ds, const int8_t* dz,
+                    hipStream_t st);
 
 // ------------------------------------------------------------------------------------------------ forward calls
 // One forward as three values (capi_forward.hip): the activations, what happens to the product, where it goes.

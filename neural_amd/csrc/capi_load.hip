@@ -11,7 +11,7 @@ using namespace nad;
 // ------------------------------------------------------------------------------------------------ load / repack
 // F8_E8M0 shared exponents become exact fp32 scales 2^e on the device; DQ8_BNB codes are decoded on the host at load
 // (dq8_get_fp_scale, kernel_ref.h:1981-1991) into the fp32 scales the reference computes
-static int scale_code(uint32_t t) {
+int scale_code(uint32_t t) {
   return (t == kF32 || t == kF8E8M0 || t == kDQ8_BNB) ? kScaleF32 : (t == kBF16 ? kScaleBF16 : kScaleF16);
 }
 // NFloat kind of the device weight: 0..2 the F4 LUTs (int4 layout), 3 F8_E4M3 / 4 F8_E5M2 (int8 layout, raw codes)
@@ -60,13 +60,44 @@ static bool scale_in_fold_range(float s, float qmax) {
   const float a = std::fabs(s);
   return a == 0.f || (a >= 6.103515625e-05f && a * qmax <= 65504.f);
 }
-static bool blob_fold_ok(const Blob& b, const uint8_t* base, int dev_bits) {
+bool blob_fold_ok(const Blob& b, const uint8_t* base, int dev_bits) {
   if (b.scale_t == kF8E8M0 || nfloat_kind(b.qtype) >= 0) return false;  // F4 / F8 weights never take gemm3 / gemm4
   const float qmax = fold_qmax(dev_bits, b.asym);
   for (int g = 0; g < b.ngroups_k(); g++)  // the padding rows and columns hold zeros
     for (int n = 0; n < b.n; n++)
       if (!scale_in_fold_range(b.scale_at(reinterpret_cast<const int8_t*>(base), g, n), qmax)) return false;
   return true;
+}
+
+// the blob's q / scale / zero-point sections, already on the device, into w's tile layout (dz null: symmetric)
+int repack_sections(const Blob& b, const DeviceWeight& w, const uint8_t* dq, const void* ds, const int8_t* dz,
+                    hipStream_t st) {
+  CoreInfo ci = core_info(b.core_id);
+  RepackArgs ra{};
+  ra.src_q = dq;
+  ra.src_s = ds;
+  ra.src_z = dz;
+  ra.ntile = ci.ntile;
+  ra.packrow = ci.packrow;
+  ra.kpad = b.kpad;
+  ra.cstep = b.cstep;
+  ra.src_bits = dtype_bits(b.qtype);
+  ra.raw = is_f8(b.qtype) ? 1 : 0;
+  ra.src_e8m0 = b.scale_t == kF8E8M0 ? 1 : 0;
+  ra.nel = uint64_t(b.npad) * b.kpad;
+  ra.bits = w.bits;
+  ra.n = w.n;
+  ra.k = w.k;
+  ra.ns = w.ns;
+  ra.nt = w.nt;
+  ra.ng = w.ng;
+  ra.scale_t = w.scale_t;
+  ra.kmajor = w.kmajor;
+  ra.dst_tiles = static_cast<uint32_t*>(w.tiles);
+  ra.dst_scales = w.scales;
+  ra.dst_zps = w.zps;
+  HIP_OK(launch_repack(ra, st));
+  return 0;
 }
 
 extern "C" int nad_device_load(const void* hostblob, void* devstor, void* deviceptr, size_t capacity, void* queue) {
@@ -122,31 +153,7 @@ extern "C" int nad_device_load(const void* hostblob, void* devstor, void* device
     HIP_OK(hipMemcpy2DAsync(w.reduce, size_t(w.red_ld) * 2, base + b.r_off, size_t(b.cstep) * 2, size_t(b.n) * 2,
                             size_t(w.ng), hipMemcpyHostToDevice, st));
   }
-  CoreInfo ci = core_info(b.core_id);
-  RepackArgs ra{};
-  ra.src_q = dq;
-  ra.src_s = ds;
-  ra.src_z = zz ? reinterpret_cast<const int8_t*>(dz) : nullptr;
-  ra.ntile = ci.ntile;
-  ra.packrow = ci.packrow;
-  ra.kpad = b.kpad;
-  ra.cstep = b.cstep;
-  ra.src_bits = dtype_bits(b.qtype);
-  ra.raw = is_f8(b.qtype) ? 1 : 0;
-  ra.src_e8m0 = b.scale_t == kF8E8M0 ? 1 : 0;
-  ra.nel = uint64_t(b.npad) * b.kpad;
-  ra.bits = w.bits;
-  ra.n = w.n;
-  ra.k = w.k;
-  ra.ns = w.ns;
-  ra.nt = w.nt;
-  ra.ng = w.ng;
-  ra.scale_t = w.scale_t;
-  ra.kmajor = w.kmajor;
-  ra.dst_tiles = static_cast<uint32_t*>(w.tiles);
-  ra.dst_scales = w.scales;
-  ra.dst_zps = w.zps;
-  HIP_OK(launch_repack(ra, st));
+  if (repack_sections(b, w, dq, ds, zz ? reinterpret_cast<const int8_t*>(dz) : nullptr, st)) return -1;
   HIP_OK(hipStreamSynchronize(st));
   HIP_OK(hipFree(stage));
   std::memcpy(devstor, &w, sizeof(w));
