@@ -181,8 +181,9 @@ int nad_device_quantize(const void* w, int w_dtype, int n, int k, int ldw, int b
                         void* blob_out, size_t blob_capacity, void* queue);
 /* descriptor summary: [magic, bits, n, k, blocksize, ns, nt, ng, scale_t, asym, has_shuffle, bytes] */
 int nad_weight_info(const void* devstor, int64_t* out12);
-/* the same, versioned by the caller's buffer: writes min(n, 13) values ([12] = fold_ok: every q * scale is an fp16
- * normal, the prefill GEMM may fold the scale into the fp16 weights), returns the number written or -1 */
+/* the same, versioned by the caller's buffer: writes min(n, 14) values ([12] = fold_ok: every q * scale is an fp16
+ * normal, the prefill GEMM may fold the scale into the fp16 weights; [13] = the tile order, 0 stripe-major [ns][nt],
+ * 1 K-major [nt][ns]), returns the number written or -1 */
 int nad_weight_info2(const void* devstor, int64_t* out, int n);
 /* re-read the NAD_* tuning / A-B switches from the environment (they are read once when the library loads, never per
  * call); not thread-safe against forwards running at the same time */
@@ -360,6 +361,38 @@ int nad_gguf_device_load(int type, const void* blocks, int n, int k, void* devst
 /* 0 and nad_last_error() unless n > 0 and k is a positive multiple of 256 */
 size_t nad_q6_k_device_size(int n, int k);
 int nad_q6_k_device_load(const void* blocks, int n, int k, void* devstor, void* deviceptr, size_t capacity, void* queue);
+/* ===== ne_get_rows on a device weight (ne_compute_forward_get_rows_q, core/ne_layers.c:8385-8433, 8529-8546: the
+ * token embedding of every model graph, models/llama/llama.cpp:189): out[r][0:k] = the dequantized weight row ids[r],
+ * i.e. row ids[r] of the [N][K] matrix the weight was quantized from -- the row the forward multiplies the activations
+ * by.  Every weight nad_device_load, nad_gguf_device_load, nad_q4_0_device_load, nad_q6_k_device_load and
+ * nad_device_quantize produce is taken (int4 / int2 / int8 tile layouts with S1..S8, F4 and F8 codes, every scale type,
+ * sym / asym / block mins, both tile orders, Q6_K) except an act-order one, refused by name: "the weight is act-order
+ * (desc_act): rows are not gathered from it".
+ *   ids   device memory, m entries ids_stride (>= 1) int32s apart: one column of an [m][top_k]-like table is
+ *         ids = table + col, ids_stride = top_k.  Read on the device when the kernel runs, never on the host.
+ *   out   device memory, [m][ldo] of out_dtype (NAD_ACT_F32 / F16 / BF16), ldo >= k counted in elements.  The rows are
+ *         written with 16-byte stores: out must be 16-byte aligned and ldo a multiple of 4 (fp32) / 8 (fp16, bf16)
+ *         elements; anything else is refused.  Exactly out[0:m, 0:k] is written.
+ * An id outside [0, n) gives a row of +0.0 and reads no weight memory (the index is clamped before any address is
+ * formed) -- the rule of an out-of-range expert in the routed entries.
+ * fp32 output has the bits of nad_device_unpack_fp32's [kk][ids[r]]: the integer formats float(v - bias - zp) * s, F4
+ * the LUT value * s, F8 f8_to_fp32's construction * s, Q4_1 / Q5_1 (q + min_bias) * d then + m each rounded on its own,
+ * Q6_K (d * sc) * q; no contraction anywhere.  fp16 / bf16 output is that fp32 value converted once, round to nearest
+ * even.
+ * One launch; no allocation, no host read of ids, no synchronisation: the call can be captured in a graph and replayed
+ * after ids has been rewritten on the device.  m = 0 launches nothing.  Returns 0, or -1 and nad_last_error(). */
+int nad_device_get_rows(const void* devstor, const int32_t* ids, int ids_stride, int m, void* out, int out_dtype,
+                        int ldo, void* queue);
+/* Dry run of nad_device_get_rows (no launch, no GPU needed; a geometry-only descriptor qualifies): out as
+ * nad_plan_weight's -- [NAD_KERNEL_GET_ROWS, grid, threads per workgroup, 1, 0, launches]; a unit of work is (row, 16 K
+ * tiles) -- Q6_K: (row, 4 superblocks) -- and a workgroup takes four.  Returns the number of values written or -1. */
+#define NAD_KERNEL_GET_ROWS 20 /* woq_get_rows_kernel / woq_get_rows_q6k_kernel: ne_get_rows on a device weight */
+int nad_plan_get_rows(const void* devstor, int m, int out_dtype, int64_t* out, int nout);
+/* A geometry-only weight descriptor for the dry runs, no GPU needed: bits 2 / 4 / 8 (blocksize <= 0 = per-channel,
+ * scale_t NAD_SCALE_*, act_order != 0: a desc_act weight) or 6 (Q6_K, k % 256 == 0; the other arguments are ignored).
+ * It holds no weights: nad_plan_get_rows and the argument checks of nad_device_get_rows take it, every entry that
+ * would launch on it refuses it by name. */
+int nad_weight_plan_only(int bits, int n, int k, int blocksize, int scale_t, int asym, int act_order, void* devstor);
 /* quantize_row_q8_1_reference (vectors/cpu/quantize.h:546-579) on device pointers: act [m][lda] -> m rows of K/32
  * blocks {float d; float s; int8 qs[32]} */
 int nad_quant_q8_1(const void* act, int act_dtype, int m, int k, int lda, void* blocks, void* queue);

@@ -103,6 +103,9 @@ SIGNATURES = {
     "nad_quant_q8_k": (_i, [_p, _i, _i, _i, _i, _p, _p]),
     "nad_q6_k_device_size": (_sz, [_i, _i]),
     "nad_q6_k_device_load": (_i, [_p, _i, _i, _p, _p, _sz, _p]),
+    "nad_device_get_rows": (_i, [_p, _p, _i, _i, _p, _i, _i, _p]),
+    "nad_plan_get_rows": (_i, [_p, _i, _i, _p, _i]),
+    "nad_weight_plan_only": (_i, [_i, _i, _i, _i, _i, _i, _i, _p]),
     "nad_batch_create": (_p, [_p, _i]),
     "nad_batch_run": (_i, [_p, _p]),
     "nad_batch_destroy": (None, [_p]),

@@ -9,6 +9,8 @@ Reference entry points mirrored (paths relative to the reference repo root):
   DeviceWeight      <- bestla_device_load_storage (ne_bestla.h:96; SYCL impl ne_bestla_sycl.cpp:94-144)
   DeviceWeight.forward / f32f32_forward
                     <- bestla_device_f32f32_forward (ne_bestla.h:97-98) / bestla_f32f32_forward (inner_product.cpp:28-36)
+  DeviceWeight.get_rows
+                    <- ne_get_rows on a quantized tensor (ne_compute_forward_get_rows_q, core/ne_layers.c:8385-8433)
   qkv_forward()     <- bestla_fusion_QKV_f32f32_forward (ip_fusion_qkv.cpp)
   ffn_forward()     <- bestla_fusion_FFN_SiLu_f32f32_forward / _Gelu_Mul_ (ip_fusion_ffn.cpp:734-755)
   ExpertBank / mul_mat_id() / moe_ffn() / moe_route()
@@ -179,7 +181,8 @@ KERNELS = {1: "woq_gemv_m1_kernel", 2: "woq_gemv_kernel", 3: "woq_skinny_kernel"
            5: "woq_gemm3_kernel", 6: "woq_gemm4_kernel", 7: "woq_gemm2_kernel", 8: "woq_gemm_kernel",
            9: "woq_gemm7_kernel", 10: "woq_mid_kernel", 11: "woq_q6k_gemv_kernel", 12: "woq_q6k_gemm_kernel",
            13: "woq_q6k_i8_kernel", 14: "woq_gemv_m1_routed_kernel", 15: "moe_combine_kernel", 16: "moe_sort_kernel",
-           17: "nad_cvt_act_kernel", 18: "woq_gemm7_grouped_kernel", 19: "moe_gather_kernel"}
+           17: "nad_cvt_act_kernel", 18: "woq_gemm7_grouped_kernel", 19: "moe_gather_kernel",
+           20: "woq_get_rows_kernel"}
 
 
 def plan_forward(bits, n, k, group_size=128, scale_dtype="fp16", asym=False, m=1, act="fp32"):
@@ -217,6 +220,30 @@ def plan_qkv(wq, wk, wv, m, act="fp32"):
     if lib().nad_plan_qkv(wq.desc, wk.desc, wv.desc, m, at, _ptr(o), 6) != 6:
         raise RuntimeError(f"nad_plan_qkv failed: {last_error()}")
     return _plan_dict(o)
+
+
+def plan_only_weight(bits, n, k, group_size=128, scale_dtype="fp16", asym=False, act_order=False):
+    """A geometry-only weight descriptor for the dry runs (nad_weight_plan_only: no GPU needed, holds no weights);
+    bits 6 is GGUF Q6_K."""
+    L = lib()
+    desc = (C.c_uint8 * L.bestla_device_storage_size())()
+    st = {"fp32": 0, "bf16": 1, "fp16": 2}[scale_dtype]
+    check(L.nad_weight_plan_only(bits, n, k, group_size, st, int(asym), int(act_order), desc), "nad_weight_plan_only")
+    return desc
+
+
+def _plan_get_rows(desc, m, dtype="fp32"):
+    o = np.zeros(6, np.int64)
+    ot = {"fp32": 0, "fp16": 1, "bf16": 2}[dtype]
+    if lib().nad_plan_get_rows(desc, m, ot, _ptr(o), 6) != 6:
+        raise RuntimeError(f"nad_plan_get_rows failed: {last_error()}")
+    return _plan_dict(o)
+
+
+def plan_get_rows(desc, m, dtype="fp32"):
+    """What get_rows of m ids on this descriptor (plan_only_weight's, or a DeviceWeight's .desc) launches: kernel, grid
+    and threads (nad_plan_get_rows -- no GPU needed)."""
+    return _plan_get_rows(desc, m, dtype)
 
 
 def _torch():
@@ -389,6 +416,34 @@ class DeviceWeight:
         if lib().nad_plan_weight(self.desc, m, at, _ptr(o), 6) != 6:
             raise RuntimeError(f"nad_plan_weight failed: {last_error()}")
         return _plan_dict(o)
+
+    def get_rows(self, ids, out=None, dtype=None, stream=None):
+        """ne_get_rows (nad_device_get_rows): out[r][0:k] = the dequantized weight row ids[r], bit for bit the columns
+        of unpack().  ids: an int32 cuda tensor, contiguous or a strided 1-D view (one column of an [m][top_k] table);
+        read on the device, so a captured call follows ids as it is rewritten.  An id outside [0, n) gives a row of
+        +0.0.  out: [m][>= k] fp32 / fp16 / bf16 with 16-byte aligned rows (default: a new [m][k] tensor of dtype,
+        fp32 when not given).  One launch, no synchronisation."""
+        torch = _torch()
+        if ids.dim() != 1 or ids.dtype != torch.int32 or not ids.is_cuda:
+            raise ValueError("get_rows takes a 1-D int32 cuda tensor of row ids")
+        m = ids.shape[0]
+        if out is None:
+            ld = -(-self.k // 8) * 8  # whole 16-byte stores for every output type
+            out = torch.empty((m, ld), dtype=dtype or torch.float32, device=ids.device)[:, :self.k]
+        elif dtype is not None and out.dtype != dtype:
+            raise TypeError(f"out is {out.dtype}, dtype asks for {dtype}")
+        if out.dim() != 2 or out.shape[0] != m or out.shape[1] != self.k or out.stride(1) != 1:
+            raise ValueError(f"out must be [{m}][{self.k}] with contiguous rows")
+        # the strides of a single row are never applied
+        stride = ids.stride(0) if m > 1 else 1
+        ldo = out.stride(0) if m > 1 else -(-self.k // 8) * 8
+        check(lib().nad_device_get_rows(self.desc, _ptr(ids), stride, m, _ptr(out), _act_code(out), ldo,
+                                        _stream(stream)), "nad_device_get_rows")
+        return out
+
+    def plan_get_rows(self, m, dtype="fp32"):
+        """what get_rows of m ids launches (nad_plan_get_rows: a dry run, nothing is launched, no GPU needed)"""
+        return _plan_get_rows(self.desc, m, dtype)
 
     def set_compute(self, mode):
         """Per-weight arithmetic (nad_device_set_compute): None / -1 follow the thread / process mode, COMPUTE_FP,

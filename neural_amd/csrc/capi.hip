@@ -156,6 +156,10 @@ const DeviceWeight* as_weight(const void* p) {
     set_err("weight descriptor is not a loaded neural_amd device weight");
     return nullptr;
   }
+  if (!w->tiles && !planning()) {  // nad_weight_plan_only: dry runs only, nothing may be launched on it
+    set_err("weight descriptor is geometry-only (nad_weight_plan_only): it holds no weights");
+    return nullptr;
+  }
   return w;
 }
 

@@ -172,16 +172,16 @@ extern "C" void bestla_device_load_storage(void* hoststor, void* devstor, void* 
   if (nad_device_load(hoststor, devstor, deviceptr, b.size, queue) != 0) report("bestla_device_load_storage");
 }
 
-// descriptor summary, versioned by the caller's buffer length: writes min(n, 13) values, returns the count written
+// descriptor summary, versioned by the caller's buffer length: writes min(n, 14) values, returns the count written
 extern "C" int nad_weight_info2(const void* devstor, int64_t* o, int n) {
   const auto* w = static_cast<const DeviceWeight*>(devstor);
   if (!w || w->magic != kWeightMagic || !o || n < 0) {
     set_err("not a neural_amd device weight descriptor (or no output buffer)");
     return -1;
   }
-  const int64_t v[13] = {w->magic, w->bits, w->n, w->k, w->blocksize, w->ns, w->nt, w->ng, w->scale_t, w->asym,
-                         w->has_shuffle, int64_t(w->bytes), w->fold_ok};
-  const int c = n < 13 ? n : 13;
+  const int64_t v[14] = {w->magic, w->bits, w->n, w->k, w->blocksize, w->ns, w->nt, w->ng, w->scale_t, w->asym,
+                         w->has_shuffle, int64_t(w->bytes), w->fold_ok, w->kmajor};
+  const int c = n < 14 ? n : 14;
   std::memcpy(o, v, sizeof(int64_t) * size_t(c));
   return c;
 }
