@@ -325,7 +325,7 @@ int nad_quant_q8_0(const void* act, int act_dtype, int m, int k, int lda, void* 
  * reproduces the reference's integer arithmetic: Q8_0 activations for Q5_0 / Q8_0 (ne_vec_dot_q5_0_q8_0,
  * ne_vec_dot_q8_0_q8_0), Q8_1 for Q4_1 / Q5_1 (ne_vec_dot_q4_1_q8_1, ne_vec_dot_q5_1_q8_1); a fused call whose weights
  * need different activation quantizers fails with a recorded error.  NAD_GGUF_Q4_0 through these entries is
- * nad_q4_0_* exactly. */
+ * the load of nad_q4_0_* exactly (one load path serves every type; an error names the entry that was called). */
 #define NAD_GGUF_Q4_0 2
 #define NAD_GGUF_Q4_1 3
 #define NAD_GGUF_Q5_0 6

@@ -309,59 +309,51 @@ class DeviceWeight:
         return cls(_desc=desc, _mem=mem)
 
     @classmethod
+    def _from_blocks(cls, size_fn, load_fn, load_name, block_bytes, block_elems, blocks, n, k, device, stream):
+        """n rows of k / block_elems GGUF blocks through one pair of C entries: size_fn(n, k) and load_fn(blocks, n, k,
+        desc, mem, capacity, queue)"""
+        torch = _torch()
+        need = size_fn(n, k)
+        if not need:
+            raise RuntimeError(last_error())
+        blocks = np.ascontiguousarray(blocks, dtype=np.uint8)
+        assert blocks.size == n * (k // block_elems) * block_bytes, (blocks.size, n, k, block_bytes)
+        mem = torch.empty(need, dtype=torch.uint8, device=device or "cuda")
+        desc = (C.c_uint8 * lib().bestla_device_storage_size())()
+        check(load_fn(_ptr(blocks), n, k, desc, _ptr(mem), need, _stream(stream)), load_name)
+        return cls(_desc=desc, _mem=mem)
+
+    @classmethod
     def from_q4_0(cls, blocks, n, k, device=None, stream=None):
         """A GGUF Q4_0 matrix (n rows of k/32 block_q4_0, as an NE_TYPE_Q4_0 ne_tensor holds it) in the device tile
         layout (nad_q4_0_device_load)."""
-        torch = _torch()
         L = lib()
-        blocks = np.ascontiguousarray(blocks, dtype=np.uint8)
-        assert blocks.size == n * (k // 32) * 18, (blocks.size, n, k)
-        need = L.nad_q4_0_device_size(n, k)
-        if not need:
-            raise RuntimeError(last_error())
-        mem = torch.empty(need, dtype=torch.uint8, device=device or "cuda")
-        desc = (C.c_uint8 * L.bestla_device_storage_size())()
-        check(L.nad_q4_0_device_load(_ptr(blocks), n, k, desc, _ptr(mem), need, _stream(stream)), "nad_q4_0_device_load")
-        return cls(_desc=desc, _mem=mem)
+        return cls._from_blocks(L.nad_q4_0_device_size, L.nad_q4_0_device_load, "nad_q4_0_device_load", 18, 32, blocks,
+                                n, k, device, stream)
 
     @classmethod
     def from_gguf(cls, type, blocks, n, k, device=None, stream=None):
         """A GGUF matrix of one of the legacy block types (GGUF_Q4_0 / Q4_1 / Q5_0 / Q5_1 / Q8_0: n rows of k/32 blocks,
         as an ne_tensor of that NE_TYPE holds it) in the device tile layout (nad_gguf_device_load); GGUF_Q6_K goes to
         from_q6_k."""
-        if int(type) == GGUF_Q6_K:  # superblocks of 256: entries of its own
+        type = int(type)
+        if type == GGUF_Q6_K:  # superblocks of 256: entries of its own
             return cls.from_q6_k(blocks, n, k, device=device, stream=stream)
-        torch = _torch()
         L = lib()
-        bb = L.nad_gguf_block_bytes(int(type))
+        bb = L.nad_gguf_block_bytes(type)
         if not bb:
             raise RuntimeError(last_error())
-        blocks = np.ascontiguousarray(blocks, dtype=np.uint8)
-        assert blocks.size == n * (k // 32) * bb, (blocks.size, n, k, bb)
-        need = L.nad_gguf_device_size(int(type), n, k)
-        if not need:
-            raise RuntimeError(last_error())
-        mem = torch.empty(need, dtype=torch.uint8, device=device or "cuda")
-        desc = (C.c_uint8 * L.bestla_device_storage_size())()
-        check(L.nad_gguf_device_load(int(type), _ptr(blocks), n, k, desc, _ptr(mem), need, _stream(stream)),
-              "nad_gguf_device_load")
-        return cls(_desc=desc, _mem=mem)
+        return cls._from_blocks(lambda n, k: L.nad_gguf_device_size(type, n, k),
+                                lambda *a: L.nad_gguf_device_load(type, *a), "nad_gguf_device_load", bb, 32, blocks, n,
+                                k, device, stream)
 
     @classmethod
     def from_q6_k(cls, blocks, n, k, device=None, stream=None):
         """A GGUF Q6_K matrix (n rows of k/256 block_q6_K of 210 bytes, as an NE_TYPE_Q6_K ne_tensor holds it) in its
         own device layout at 6.5625 bits per weight (nad_q6_k_device_load)."""
-        torch = _torch()
         L = lib()
-        need = L.nad_q6_k_device_size(n, k)
-        if not need:
-            raise RuntimeError(last_error())
-        blocks = np.ascontiguousarray(blocks, dtype=np.uint8)
-        assert blocks.size == n * (k // 256) * 210, (blocks.size, n, k)
-        mem = torch.empty(need, dtype=torch.uint8, device=device or "cuda")
-        desc = (C.c_uint8 * L.bestla_device_storage_size())()
-        check(L.nad_q6_k_device_load(_ptr(blocks), n, k, desc, _ptr(mem), need, _stream(stream)), "nad_q6_k_device_load")
-        return cls(_desc=desc, _mem=mem)
+        return cls._from_blocks(L.nad_q6_k_device_size, L.nad_q6_k_device_load, "nad_q6_k_device_load", 210, 256, blocks,
+                                n, k, device, stream)
 
     @classmethod
     def quantize(cls, w, group_size=32, weight_dtype="int4", scale_dtype="fp32", alg="sym", compute_dtype="int8",

@@ -163,6 +163,13 @@ const DeviceWeight* as_weight(const void* p) {
   return w;
 }
 
+// ------------------------------------------------------------------------------------------------ staging
+int staging_finish(const char* who, Staging& s) {
+  if (s.finish() == hipSuccess) return 0;
+  set_err("%s: %s failed: %s", who, s.what(), hipGetErrorString(s.error()));
+  return -1;
+}
+
 // ------------------------------------------------------------------------------------------------ workspace
 // Device workspace for the prefill GEMM's fp16 copy of the activations, in order of preference:
 //   1. the caller's workspace of a reference entry point (bestla_device_f32f32_forward(..., workspace, queue): the
@@ -243,24 +250,13 @@ static int compute_mode() {
   }
   return m;
 }
-// NAD_GGUF_* of a loaded weight, 0 for a weight that is no GGUF matrix
-static int gguf_type(const DeviceWeight& w) {
-  switch (w.src_core_id) {
-    case kGgufQ4_0: return NAD_GGUF_Q4_0;
-    case kGgufQ4_1: return NAD_GGUF_Q4_1;
-    case kGgufQ5_0: return NAD_GGUF_Q5_0;
-    case kGgufQ5_1: return NAD_GGUF_Q5_1;
-    case kGgufQ8_0: return NAD_GGUF_Q8_0;
-    default: return 0;
-  }
-}
 int gguf_act_quant(const DeviceWeight& w) {
-  const int t = gguf_type(w);
-  return t == 0 ? 0 : ((t == NAD_GGUF_Q4_1 || t == NAD_GGUF_Q5_1) ? 2 : 1);
+  const GgufType* t = gguf_type_by_tag(w.src_core_id);  // null: no GGUF matrix
+  return t ? t->act_quant : 0;
 }
 static int effective_mode(const DeviceWeight& w) { return w.compute > 0 ? w.compute - 1 : compute_mode(); }
 bool int8_compute(const DeviceWeight& w) {
-  return effective_mode(w) == 1 && (w.reduce != nullptr || gguf_type(w) != 0);
+  return effective_mode(w) == 1 && (w.reduce != nullptr || gguf_act_quant(w) != 0);
 }
 // Mode 2 (NAD_COMPUTE_Q8_K) is a GGUF Q6_K weight's own setting only: the reference's Q8_K activation rows and
 // ggml_vec_dot_q6_K_q8_K integer dot product (woq_q6k_i8_kernel).  The thread and process modes keep their two values,

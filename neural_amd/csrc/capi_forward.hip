@@ -273,14 +273,14 @@ static int i8_quantize(I8Act& r, char* ws, const Act& x, const DeviceWeight& w, 
   r.m = x.m;
   r.k = x.k;
   if (const int aq = gguf_act_quant(w)) {  // Q8_0 / Q8_1 rows (quantize_row_q8_0_reference / quantize_row_q8_1_reference)
-    Q80Args q{};
+    Q8Args q{};
     fill_act(q, x);
     q.aq = const_cast<int8_t*>(r.aq);
     q.ldq = kp;
     q.kp = kp;
     q.sa = const_cast<float2*>(r.sa);
     return launch(planned_pass(), "Q8_0 / Q8_1 activation quantization",
-                  [&] { return aq == 2 ? launch_q8_1_quant(q, x.t, st) : launch_q8_0_quant(q, x.t, st); })
+                  [&] { return launch_q8_quant(q, aq == 2, x.t, st); })
                ? 0
                : -1;
   }

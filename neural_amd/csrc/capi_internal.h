@@ -9,6 +9,7 @@
 
 #include "../../include/neural_amd.h"
 #include "btla_format.h"
+#include "staging.h"
 #include "woq_kernels.h"
 
 #pragma GCC visibility push(hidden)
@@ -78,22 +79,28 @@ struct CallWorkspace {  // RAII binding of a reference call's workspace argument
 };
 
 // ------------------------------------------------------------------------------------------------ compute mode (capi.hip)
-// a GGUF Q4_0 matrix (nad_q4_0_device_load) carries this in src_core_id: its int8 arithmetic is Q8_0 x Q4_0
-constexpr uint64_t kGgufQ4_0 = 0x3054344655474700ull;  // "\0GGUF4Q0"
-// the other GGUF block types (nad_gguf_device_load): the same tag with the type's two characters
-constexpr uint64_t kGgufQ4_1 = 0x3154344655474700ull;  // "\0GGUF4Q1"
-constexpr uint64_t kGgufQ5_0 = 0x3054354655474700ull;  // "\0GGUF5Q0"
-constexpr uint64_t kGgufQ5_1 = 0x3154354655474700ull;  // "\0GGUF5Q1"
-constexpr uint64_t kGgufQ8_0 = 0x3054384655474700ull;  // "\0GGUF8Q0"
-// GGUF Q6_K (nad_q6_k_device_load): bits = 6, a layout and forward kernels of its own (woq_q6k.hip); fp arithmetic, or the
-// reference's Q8_K integer arithmetic as the weight's own mode 2
-constexpr uint64_t kGgufQ6_K = 0x4b51364655474700ull;  // "\0GGUF6QK"
+// a GGUF matrix carries its type's tag in src_core_id (woq_gguf.h: kGgufTypes).  The 32-element types run the
+// reference's Q8_0 / Q8_1 arithmetic in int8 mode; Q6_K (bits = 6, a layout and forward kernels of its own, woq_q6k.hip)
+// runs fp arithmetic, or the reference's Q8_K integer arithmetic as the weight's own mode 2
 inline bool is_q6k(const nad::DeviceWeight& w) { return w.bits == 6; }
 // the activation quantizer of the weight's int8 arithmetic (its vec_dot_type, ne_layers.c:266-318): 0 the kblock
 // core's u8, 1 Q8_0 (Q4_0, Q5_0, Q8_0), 2 Q8_1 (Q4_1, Q5_1)
 int gguf_act_quant(const nad::DeviceWeight& w);
 bool int8_compute(const nad::DeviceWeight& w);  // a forward of this weight takes the int8 arithmetic right now
 bool q8k_compute(const nad::DeviceWeight& w);   // a Q6_K weight set to NAD_COMPUTE_Q8_K: forward_q6k takes woq_q6k_i8_kernel
+
+// ------------------------------------------------------------------------------------------------ staging (capi.hip)
+struct HipStagingApi {
+  using Error = hipError_t;
+  using Stream = hipStream_t;
+  static constexpr Error kOk = hipSuccess;
+  static Error malloc(void** p, size_t bytes) { return hipMalloc(p, bytes); }
+  static Error sync(Stream st) { return hipStreamSynchronize(st); }
+  static Error free(void* p) { return hipFree(p); }
+};
+using Staging = nad::StagingBuffer<HipStagingApi>;
+// s.finish(); 0, or -1 with "<who>: <first failing step> failed: <HIP error>" set
+int staging_finish(const char* who, Staging& s);
 
 // ------------------------------------------------------------------------------------------------ load (capi_load.hip)
 // base: the host blob, scanned for codes the device cannot hold (load time only; null skips the scan)

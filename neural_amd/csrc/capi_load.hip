@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "capi_internal.h"
+#include "woq_device.h"
 
 using namespace nad;
 
@@ -131,8 +132,7 @@ extern "C" int nad_device_load(const void* hostblob, void* devstor, void* device
   w.fold_ok = blob_fold_ok(b, static_cast<const uint8_t*>(hostblob), w.bits) ? 1 : 0;
   // stage the raw blob buffers on the device, repack there
   const uint8_t* base = static_cast<const uint8_t*>(hostblob);
-  uint8_t* stage = nullptr;
-  std::vector<float> dqs;  // DQ8_BNB: the decoded fp32 scales [ngroups][cstep], zero padding
+  std::vector<float> dqs;  // DQ8_BNB: the decoded fp32 scales [ngroups][cstep], zero padding (outlives the staging)
   if (b.has_dq) {
     dqs.assign(size_t(b.ngroups()) * b.cstep, 0.f);
     for (int g = 0; g < b.ngroups_k(); g++)
@@ -140,9 +140,10 @@ extern "C" int nad_device_load(const void* hostblob, void* devstor, void* device
   }
   const uint8_t* shost = b.has_dq ? reinterpret_cast<const uint8_t*>(dqs.data()) : base + b.s_off;
   const uint64_t qz = b.q_size, sz = b.has_dq ? dqs.size() * 4 : b.s_size, zz = b.asym ? b.z_size : 0;
-  HIP_OK(hipMalloc(&stage, align256(qz) + align256(sz) + align256(zz) + 256));
-  uint8_t* dq = stage;
-  uint8_t* ds = stage + align256(qz);
+  Staging stage(st);  // every return below synchronises, then frees
+  if (!stage.alloc(align256(qz) + align256(sz) + align256(zz) + 256)) return staging_finish("nad_device_load", stage);
+  uint8_t* dq = stage.ptr();
+  uint8_t* ds = dq + align256(qz);
   uint8_t* dz = ds + align256(sz);
   HIP_OK(hipMemcpyAsync(dq, base + b.q_off, qz, hipMemcpyHostToDevice, st));
   HIP_OK(hipMemcpyAsync(ds, shost, sz, hipMemcpyHostToDevice, st));
@@ -154,8 +155,7 @@ extern "C" int nad_device_load(const void* hostblob, void* devstor, void* device
                             size_t(w.ng), hipMemcpyHostToDevice, st));
   }
   if (repack_sections(b, w, dq, ds, zz ? reinterpret_cast<const int8_t*>(dz) : nullptr, st)) return -1;
-  HIP_OK(hipStreamSynchronize(st));
-  HIP_OK(hipFree(stage));
+  if (staging_finish("nad_device_load", stage)) return -1;
   std::memcpy(devstor, &w, sizeof(w));
   return 0;
 }
@@ -233,258 +233,149 @@ extern "C" int nad_quant_u8_colblock(const void* act, int act_dtype, int m, int 
   return 0;
 }
 
-// ------------------------------------------------------------------------------------------------ GGUF Q4_0
-extern "C" size_t nad_q4_0_device_size(int n, int k) {
-  if (n <= 0 || k <= 0 || k % 32) {
-    set_err("Q4_0 needs n > 0 and k a positive multiple of 32 (n=%d k=%d)", n, k);
-    return 0;
-  }
-  DeviceWeight w{};
-  return layout_geometry(w, 4, n, k, 32, kScaleF16, false, false);
+// ------------------------------------------------------------------------------------------------ GGUF block types
+// One load path for every row of kGgufTypes (woq_gguf.h); the exported entries below name themselves in `who`.
+extern "C" size_t nad_gguf_block_bytes(int type) {
+  const GgufType* t = gguf_type_by_id(type);
+  if (t && t->block_elems == 32) return size_t(t->block_bytes);
+  if (t)  // superblocks of 256, not blocks of 32: entries of its own
+    set_err("GGUF type %d (%s) has no 32-element block: it loads through nad_q6_k_device_size / nad_q6_k_device_load",
+            t->id, t->name);
+  else
+    set_err("GGUF type %d is not supported (Q4_0 = 2, Q4_1 = 3, Q5_0 = 6, Q5_1 = 7, Q8_0 = 8; Q6_K = 14 through "
+            "nad_q6_k_device_load)", type);
+  return 0;
 }
 
-extern "C" int nad_q4_0_device_load(const void* blocks, int n, int k, void* devstor, void* deviceptr, size_t capacity,
-                                    void* queue) {
-  const size_t need = nad_q4_0_device_size(n, k);
+// geometry of an n x k matrix of type t and its device bytes (0, with the error set, for a bad shape): the type's
+// layout, and behind it the fp16 mins of Q4_1 / Q5_1 at *mins_off
+static uint64_t gguf_geometry(const char* who, const GgufType& t, int n, int k, DeviceWeight& w, uint64_t* mins_off) {
+  if (n <= 0 || k <= 0 || k % t.block_elems) {
+    set_err("%s: %s needs n > 0 and k a positive multiple of %d (n=%d k=%d)", who, t.name, t.block_elems, n, k);
+    return 0;
+  }
+  if (t.bits == 6) return q6k_geometry(w, n, k);
+  const uint64_t base = layout_geometry(w, t.bits, n, k, 32, kScaleF16, false, false);
+  *mins_off = base;
+  return base + (t.has_min ? align256(uint64_t(w.ns) * w.ng * 16 * 2) : 0);
+}
+
+static size_t gguf_size(const char* who, const GgufType& t, int n, int k) {
+  DeviceWeight w{};
+  uint64_t mins_off;
+  return gguf_geometry(who, t, n, k, w, &mins_off);
+}
+
+// every block starts with its fp16 d: each inside the fold range for the type's largest |decoded value|
+static bool blocks_fold_ok(const void* blocks, size_t block_bytes, size_t count, float qmax) {
+  const uint8_t* bp = static_cast<const uint8_t*>(blocks);
+  for (size_t i = 0; i < count; i++) {
+    uint16_t h;
+    std::memcpy(&h, bp + block_bytes * i, 2);
+    if (!scale_in_fold_range(float(__builtin_bit_cast(_Float16, h)), qmax)) return false;
+  }
+  return true;
+}
+
+static int gguf_load(const char* who, const GgufType& t, const void* blocks, int n, int k, void* devstor,
+                     void* deviceptr, size_t capacity, void* queue) {
+  DeviceWeight w{};
+  uint64_t mins_off = 0;
+  const size_t need = gguf_geometry(who, t, n, k, w, &mins_off);
   if (!need) return -1;
   if (!blocks || !devstor || !deviceptr || capacity < need) {
-    set_err("nad_q4_0_device_load: null pointer or device buffer too small (need %zu, have %zu)", need, capacity);
+    set_err("%s: null pointer or device buffer too small (need %zu, have %zu)", who, need, capacity);
     return -1;
   }
   hipStream_t st = static_cast<hipStream_t>(queue);
-  DeviceWeight w{};
-  layout_geometry(w, 4, n, k, 32, kScaleF16, false, false);
-  layout_assign(w, deviceptr);
-  w.src_core_id = kGgufQ4_0;
-  w.owner = nullptr;
-  {  // block_q4_0: fp16 d, then 16 bytes of nibbles; q in [-8, 7]
-    const uint8_t* bp = static_cast<const uint8_t*>(blocks);
-    bool ok = true;
-    for (size_t i = 0; ok && i < size_t(n) * (k / 32); i++) {
-      uint16_t h;
-      std::memcpy(&h, bp + 18 * i, 2);
-      ok = scale_in_fold_range(float(__builtin_bit_cast(_Float16, h)), 8.f);
+  if (is_q6k(w)) {
+    q6k_assign(w, deviceptr);
+  } else {
+    layout_assign(w, deviceptr);
+    if (t.has_min) {
+      w.mins = static_cast<char*>(deviceptr) + mins_off;
+      w.bytes = need;
+      w.min_bias = t.min_bias;
     }
-    w.fold_ok = ok ? 1 : 0;
   }
-  // padding columns / K tiles: nibble 8 = q 0, scale 0
-  HIP_OK(hipMemsetAsync(w.tiles, 0x88, size_t(w.ns) * w.nt * 1024, st));
-  HIP_OK(hipMemsetAsync(w.scales, 0, size_t(w.ns) * w.ng * 16 * 2, st));
-  const size_t bytes = size_t(n) * (k / 32) * 18;
-  uint8_t* stage = nullptr;
-  HIP_OK(hipMalloc(&stage, bytes));
-  HIP_OK(hipMemcpyAsync(stage, blocks, bytes, hipMemcpyHostToDevice, st));
-  hipError_t e = launch_q4_0_repack(stage, n, k, w, st);
-  HIP_OK(hipStreamSynchronize(st));
-  HIP_OK(hipFree(stage));
-  if (e != hipSuccess) {
-    set_err("Q4_0 repack launch failed: %s", hipGetErrorString(e));
-    return -1;
+  w.owner = nullptr;
+  w.src_core_id = t.tag;
+  const size_t count = size_t(n) * (k / t.block_elems), bytes = count * t.block_bytes;
+  // qmax 0 (Q6_K): sc * q is folded by the Q6_K GEMM itself (|sc * q| <= 4096 always fits fp16), d never
+  w.fold_ok = t.qmax > 0.f && blocks_fold_ok(blocks, t.block_bytes, count, t.qmax) ? 1 : 0;
+  Staging stage(st);
+  if (!is_q6k(w)) {  // padding columns / K tiles decode to 0: int8 byte 128, nibble 8; scale 0, min 0 (the Q6_K repack
+                     // writes every byte of its layout itself)
+    const size_t entries = size_t(w.ns) * w.ng * 16;
+    stage.run("hipMemsetAsync of the padding", [&] {
+      hipError_t e = hipMemsetAsync(w.tiles, w.bits == 4 ? 0x88 : 0x80, size_t(w.ns) * w.nt * 1024, st);
+      if (e == hipSuccess) e = hipMemsetAsync(w.scales, 0, entries * 2, st);
+      if (e == hipSuccess && w.mins) e = hipMemsetAsync(w.mins, 0, entries * 2, st);
+      return e;
+    });
   }
+  stage.alloc(bytes);
+  stage.run("hipMemcpyAsync of the blocks",
+            [&] { return hipMemcpyAsync(stage.ptr(), blocks, bytes, hipMemcpyHostToDevice, st); });
+  stage.run("repack launch", [&] {
+    return is_q6k(w) ? launch_q6k_repack(stage.ptr(), n, k, w, st) : launch_gguf_repack(t.id, stage.ptr(), n, k, w, st);
+  });
+  if (staging_finish(who, stage)) return -1;
   std::memcpy(devstor, &w, sizeof(w));
   return 0;
-}
-
-extern "C" int nad_quant_q8_0(const void* act, int act_dtype, int m, int k, int lda, void* blocks, void* queue) {
-  if (m <= 0 || k <= 0 || k % 32 || lda < k || !blocks) {
-    set_err("nad_quant_q8_0: bad arguments (m=%d k=%d lda=%d)", m, k, lda);
-    return -1;
-  }
-  Q80Args a{};
-  a.A = act;
-  a.lda = lda;
-  a.M = m;
-  a.K = k;
-  a.blocks = static_cast<int8_t*>(blocks);
-  hipError_t e = launch_q8_0_quant(a, act_dtype, static_cast<hipStream_t>(queue));
-  if (e != hipSuccess) {
-    set_err("Q8_0 quantization launch failed: %s", hipGetErrorString(e));
-    return -1;
-  }
-  return 0;
-}
-
-// ------------------------------------------------------------------------------- GGUF Q4_1 / Q5_0 / Q5_1 / Q8_0
-extern "C" size_t nad_gguf_block_bytes(int type) {
-  switch (type) {
-    case NAD_GGUF_Q4_0: return 18;
-    case NAD_GGUF_Q4_1: return 20;
-    case NAD_GGUF_Q5_0: return 22;
-    case NAD_GGUF_Q5_1: return 24;
-    case NAD_GGUF_Q8_0: return 34;
-    case NAD_GGUF_Q6_K:  // superblocks of 256, not blocks of 32: entries of its own
-      set_err("GGUF type 14 (Q6_K) has no 32-element block: it loads through nad_q6_k_device_size / nad_q6_k_device_load");
-      return 0;
-    default:
-      set_err("GGUF type %d is not supported (Q4_0 = 2, Q4_1 = 3, Q5_0 = 6, Q5_1 = 7, Q8_0 = 8; Q6_K = 14 through "
-              "nad_q6_k_device_load)", type);
-      return 0;
-  }
-}
-
-// geometry of a GGUF matrix of the four new types: Q4_1 in the symmetric int4 layout, the others in the symmetric int8
-// layout; the fp16 mins of Q4_1 / Q5_1 follow the layout's own regions
-static uint64_t gguf_geometry(DeviceWeight& w, int type, int n, int k, uint64_t* mins_off) {
-  const bool q41 = type == NAD_GGUF_Q4_1;
-  const uint64_t base = layout_geometry(w, q41 ? 4 : 8, n, k, 32, kScaleF16, false, false);
-  const bool has_m = q41 || type == NAD_GGUF_Q5_1;
-  if (mins_off) *mins_off = base;
-  return base + (has_m ? align256(uint64_t(w.ns) * w.ng * 16 * 2) : 0);
 }
 
 extern "C" size_t nad_gguf_device_size(int type, int n, int k) {
-  if (!nad_gguf_block_bytes(type)) return 0;
-  if (type == NAD_GGUF_Q4_0) return nad_q4_0_device_size(n, k);
-  if (n <= 0 || k <= 0 || k % 32) {
-    set_err("a GGUF matrix needs n > 0 and k a positive multiple of 32 (type=%d n=%d k=%d)", type, n, k);
-    return 0;
-  }
-  DeviceWeight w{};
-  return gguf_geometry(w, type, n, k, nullptr);
+  return nad_gguf_block_bytes(type) ? gguf_size("nad_gguf_device_size", *gguf_type_by_id(type), n, k) : 0;
 }
-
 extern "C" int nad_gguf_device_load(int type, const void* blocks, int n, int k, void* devstor, void* deviceptr,
                                     size_t capacity, void* queue) {
-  const size_t bb = nad_gguf_block_bytes(type);
-  if (!bb) return -1;
-  if (type == NAD_GGUF_Q4_0) return nad_q4_0_device_load(blocks, n, k, devstor, deviceptr, capacity, queue);
-  const size_t need = nad_gguf_device_size(type, n, k);
-  if (!need) return -1;
-  if (!blocks || !devstor || !deviceptr || capacity < need) {
-    set_err("nad_gguf_device_load: null pointer or device buffer too small (need %zu, have %zu)", need, capacity);
-    return -1;
-  }
-  hipStream_t st = static_cast<hipStream_t>(queue);
-  DeviceWeight w{};
-  uint64_t mins_off = 0;
-  const uint64_t total = gguf_geometry(w, type, n, k, &mins_off);
-  layout_assign(w, deviceptr);
-  const bool has_m = total > mins_off;
-  if (has_m) {
-    w.mins = static_cast<char*>(deviceptr) + mins_off;
-    w.bytes = total;
-    w.min_bias = type == NAD_GGUF_Q4_1 ? 8 : 0;  // the nibble holds q, the layout decodes q - 8
-  }
-  w.owner = nullptr;
-  w.src_core_id = type == NAD_GGUF_Q4_1 ? kGgufQ4_1
-                  : type == NAD_GGUF_Q5_0 ? kGgufQ5_0
-                  : type == NAD_GGUF_Q5_1 ? kGgufQ5_1
-                                          : kGgufQ8_0;
-  {  // every block starts with the fp16 d; the largest |decoded value| of the type
-    const float qmax = type == NAD_GGUF_Q4_1 ? 8.f : (type == NAD_GGUF_Q5_0 ? 16.f : (type == NAD_GGUF_Q5_1 ? 31.f : 128.f));
-    const uint8_t* bp = static_cast<const uint8_t*>(blocks);
-    bool ok = true;
-    for (size_t i = 0; ok && i < size_t(n) * (k / 32); i++) {
-      uint16_t h;
-      std::memcpy(&h, bp + bb * i, 2);
-      ok = scale_in_fold_range(float(__builtin_bit_cast(_Float16, h)), qmax);
-    }
-    w.fold_ok = ok ? 1 : 0;
-  }
-  // padding columns / K tiles decode to 0: int8 byte 128, nibble 8; scale 0, min 0
-  const size_t entries = size_t(w.ns) * w.ng * 16;
-  HIP_OK(hipMemsetAsync(w.tiles, w.bits == 4 ? 0x88 : 0x80, size_t(w.ns) * w.nt * 1024, st));
-  HIP_OK(hipMemsetAsync(w.scales, 0, entries * 2, st));
-  if (w.mins) HIP_OK(hipMemsetAsync(w.mins, 0, entries * 2, st));
-  const size_t bytes = size_t(n) * (k / 32) * bb;
-  uint8_t* stage = nullptr;
-  HIP_OK(hipMalloc(&stage, bytes));
-  // copy, repack, wait; the staging buffer is freed on every way out
-  const char* what = "hipMemcpyAsync of the blocks";
-  hipError_t e = hipMemcpyAsync(stage, blocks, bytes, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) {
-    what = "GGUF repack launch";
-    e = launch_gguf_repack(type, stage, n, k, w, st);
-  }
-  const hipError_t es = hipStreamSynchronize(st);  // also after a failure: the copy may still read `blocks`
-  if (e == hipSuccess && es != hipSuccess) {
-    what = "hipStreamSynchronize";
-    e = es;
-  }
-  const hipError_t ef = hipFree(stage);
-  if (e == hipSuccess && ef != hipSuccess) {
-    what = "hipFree of the staging buffer";
-    e = ef;
-  }
-  if (e != hipSuccess) {
-    set_err("nad_gguf_device_load: %s failed: %s", what, hipGetErrorString(e));
-    return -1;
-  }
-  std::memcpy(devstor, &w, sizeof(w));
-  return 0;
+  if (!nad_gguf_block_bytes(type)) return -1;  // the 32-element types; Q6_K keeps to its own entries
+  return gguf_load("nad_gguf_device_load", *gguf_type_by_id(type), blocks, n, k, devstor, deviceptr, capacity, queue);
 }
-
-// ------------------------------------------------------------------------------------------------ GGUF Q6_K
+extern "C" size_t nad_q4_0_device_size(int n, int k) {
+  return gguf_size("nad_q4_0_device_size", *gguf_type_by_id(NAD_GGUF_Q4_0), n, k);
+}
+extern "C" int nad_q4_0_device_load(const void* blocks, int n, int k, void* devstor, void* deviceptr, size_t capacity,
+                                    void* queue) {
+  return gguf_load("nad_q4_0_device_load", *gguf_type_by_id(NAD_GGUF_Q4_0), blocks, n, k, devstor, deviceptr, capacity,
+                   queue);
+}
 extern "C" size_t nad_q6_k_device_size(int n, int k) {
-  if (n <= 0 || k <= 0 || k % 256) {
-    set_err("Q6_K needs n > 0 and k a positive multiple of 256 (n=%d k=%d)", n, k);
-    return 0;
-  }
-  DeviceWeight w{};
-  return q6k_geometry(w, n, k);
+  return gguf_size("nad_q6_k_device_size", *gguf_type_by_id(NAD_GGUF_Q6_K), n, k);
 }
-
 extern "C" int nad_q6_k_device_load(const void* blocks, int n, int k, void* devstor, void* deviceptr, size_t capacity,
                                     void* queue) {
-  const size_t need = nad_q6_k_device_size(n, k);
-  if (!need) return -1;
-  if (!blocks || !devstor || !deviceptr || capacity < need) {
-    set_err("nad_q6_k_device_load: null pointer or device buffer too small (need %zu, have %zu)", need, capacity);
-    return -1;
-  }
-  hipStream_t st = static_cast<hipStream_t>(queue);
-  DeviceWeight w{};
-  q6k_geometry(w, n, k);
-  q6k_assign(w, deviceptr);
-  w.src_core_id = kGgufQ6_K;
-  w.owner = nullptr;
-  w.fold_ok = 0;  // sc * q is folded by the Q6_K GEMM itself (|sc * q| <= 4096 always fits fp16), d never
-  const size_t bytes = size_t(n) * (k / 256) * 210;
-  uint8_t* stage = nullptr;
-  HIP_OK(hipMalloc(&stage, bytes));
-  // copy, repack (it writes every byte of the layout, the padding columns included), wait; the staging buffer is
-  // freed on every way out
-  const char* what = "hipMemcpyAsync of the blocks";
-  hipError_t e = hipMemcpyAsync(stage, blocks, bytes, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) {
-    what = "Q6_K repack launch";
-    e = launch_q6k_repack(stage, n, k, w, st);
-  }
-  const hipError_t es = hipStreamSynchronize(st);
-  if (e == hipSuccess && es != hipSuccess) {
-    what = "hipStreamSynchronize";
-    e = es;
-  }
-  const hipError_t ef = hipFree(stage);
-  if (e == hipSuccess && ef != hipSuccess) {
-    what = "hipFree of the staging buffer";
-    e = ef;
-  }
-  if (e != hipSuccess) {
-    set_err("nad_q6_k_device_load: %s failed: %s", what, hipGetErrorString(e));
-    return -1;
-  }
-  std::memcpy(devstor, &w, sizeof(w));
-  return 0;
+  return gguf_load("nad_q6_k_device_load", *gguf_type_by_id(NAD_GGUF_Q6_K), blocks, n, k, devstor, deviceptr, capacity,
+                   queue);
 }
 
-extern "C" int nad_quant_q8_1(const void* act, int act_dtype, int m, int k, int lda, void* blocks, void* queue) {
+// ------------------------------------------------------------------------------------------------ activation rows
+// Q8_0 (q8_1 false) / Q8_1 blocks of the activation rows, as the reference's vec_dot reads them
+static int quant_q8(const char* who, bool q8_1, const void* act, int act_dtype, int m, int k, int lda, void* blocks,
+                    void* queue) {
   if (m <= 0 || k <= 0 || k % 32 || lda < k || !blocks) {
-    set_err("nad_quant_q8_1: bad arguments (m=%d k=%d lda=%d)", m, k, lda);
+    set_err("%s: bad arguments (m=%d k=%d lda=%d)", who, m, k, lda);
     return -1;
   }
-  Q81Args a{};
+  Q8Args a{};
   a.A = act;
   a.lda = lda;
   a.M = m;
   a.K = k;
   a.blocks = static_cast<int8_t*>(blocks);
-  hipError_t e = launch_q8_1_quant(a, act_dtype, static_cast<hipStream_t>(queue));
+  const hipError_t e = launch_q8_quant(a, q8_1, act_dtype, static_cast<hipStream_t>(queue));
   if (e != hipSuccess) {
-    set_err("Q8_1 quantization launch failed: %s", hipGetErrorString(e));
+    set_err("%s: quantization launch failed: %s", who, hipGetErrorString(e));
     return -1;
   }
   return 0;
+}
+extern "C" int nad_quant_q8_0(const void* act, int act_dtype, int m, int k, int lda, void* blocks, void* queue) {
+  return quant_q8("nad_quant_q8_0", false, act, act_dtype, m, k, lda, blocks, queue);
+}
+extern "C" int nad_quant_q8_1(const void* act, int act_dtype, int m, int k, int lda, void* blocks, void* queue) {
+  return quant_q8("nad_quant_q8_1", true, act, act_dtype, m, k, lda, blocks, queue);
 }
 
 extern "C" int nad_quant_q8_k(const void* act, int act_dtype, int m, int k, int lda, void* blocks, void* queue) {
@@ -578,18 +469,6 @@ extern "C" int nad_synthetic_weight(void* devstor, void* deviceptr, size_t capac
   return 0;
 }
 
-static __constant__ float kF4LutF[3][16] = {
-    {0.00000000f, 5.208333333e-03f, 0.66666667f, 1.00000000f, 0.33333333f, 0.50000000f, 0.16666667f, 0.25000000f,
-     -1.f * 0.00000000f, -1.f * 5.208333333e-03f, -1.f * 0.66666667f, -1.f * 1.00000000f, -1.f * 0.33333333f,
-     -1.f * 0.50000000f, -1.f * 0.16666667f, -1.f * 0.25000000f},
-    {0.f, 0.010416666666666666f, 0.16666666666666666f, 0.25f, 0.333333333333333f, 0.5f, 0.6666666666666f, 1.f,
-     -1.f * 0.f, -1.f * 0.010416666666666666f, -1.f * 0.16666666666666666f, -1.f * 0.25f, -1.f * 0.333333333333333f,
-     -1.f * 0.5f, -1.f * 0.6666666666666f, -1.f * 1.f},
-    {0.f, -0.6961928009986877f, -0.5250730514526367f, -0.39491748809814453f, -0.28444138169288635f,
-     -0.18477343022823334f, -0.09105003625154495f, -1.f, 0.07958029955625534f, 0.16093020141124725f,
-     0.24611230194568634f, 0.33791524171829224f, 0.44070982933044434f, 0.5626170039176941f, 0.7229568362236023f,
-     1.0f}};
-
 // dequantize the device tile layout back to fp32 [K][N] (exactness check of the repack)
 __global__ void nad_unrepack_kernel(DeviceWeight w, float* out) {
   const int KT = tile_k(w.bits);
@@ -616,13 +495,7 @@ __global__ void nad_unrepack_kernel(DeviceWeight w, float* out) {
     }
     const int g = kk / w.blocksize;
     const uint64_t si = scale_row(w.kmajor, w.ns, w.ng, s, g) * 16 + c;
-    float sc;
-    if (w.scale_t == kScaleF32)
-      sc = static_cast<const float*>(w.scales)[si];
-    else if (w.scale_t == kScaleBF16)
-      sc = __uint_as_float(uint32_t(static_cast<const uint16_t*>(w.scales)[si]) << 16);
-    else
-      sc = float(static_cast<const _Float16*>(w.scales)[si]);
+    const float sc = load_scale(w.scales, si, w.scale_t);
     const int zp = w.zps ? int(w.zps[si]) : 0;
     float q;
     if (w.f4kind >= 3) {  // F8 raw code (f8_to_fp32, kernel_ref.h:984-1001)
@@ -643,9 +516,10 @@ extern "C" int nad_device_unpack_fp32(const void* devstor, float* host_out, void
   const DeviceWeight* w = as_weight(devstor);
   if (!w) return -1;
   hipStream_t st = static_cast<hipStream_t>(queue);
-  float* d = nullptr;
-  size_t bytes = size_t(w->n) * w->k * 4;
-  HIP_OK(hipMalloc(&d, bytes));
+  const size_t bytes = size_t(w->n) * w->k * 4;
+  Staging stage(st);  // host_out is the caller's: every return waits for the copy into it
+  if (!stage.alloc(bytes)) return staging_finish("nad_device_unpack_fp32", stage);
+  float* d = reinterpret_cast<float*>(stage.ptr());
   if (is_q6k(*w)) {
     HIP_OK(launch_q6k_unpack(*w, d, st));
   } else {
@@ -653,7 +527,5 @@ extern "C" int nad_device_unpack_fp32(const void* devstor, float* host_out, void
     HIP_OK(hipGetLastError());
   }
   HIP_OK(hipMemcpyAsync(host_out, d, bytes, hipMemcpyDeviceToHost, st));
-  HIP_OK(hipStreamSynchronize(st));
-  HIP_OK(hipFree(d));
-  return 0;
+  return staging_finish("nad_device_unpack_fp32", stage);
 }

@@ -85,13 +85,6 @@ bool plan_quantize(const char* who, int n, int k, int blocksize, uint32_t qtype,
   return true;
 }
 
-struct DeviceScratch {  // freed on every way out
-  uint8_t* p = nullptr;
-  ~DeviceScratch() {
-    if (p) (void)hipFree(p);
-  }
-};
-
 }  // namespace
 
 extern "C" size_t nad_device_quantize_size(int n, int k, int blocksize, uint32_t qtype, uint32_t scale_dtype, int asym,
@@ -145,10 +138,11 @@ extern "C" int nad_device_quantize(const void* wsrc, int w_dtype, int n, int k, 
   const uint64_t ldq = (uint64_t(k) + 15) & ~uint64_t(15);
   const uint64_t cz = align256(uint64_t(n) * ldq), qz = align256(b.q_size), sz = align256(b.s_size),
                  zz = b.asym ? align256(b.z_size) : 0, rz = b.has_reduce ? align256(b.r_size) : 0;
-  DeviceScratch stage;
-  HIP_OK(hipMalloc(&stage.p, cz + qz + sz + zz + rz));
-  int8_t* dcodes = reinterpret_cast<int8_t*>(stage.p);
-  uint8_t* dq = stage.p + cz;
+  std::vector<uint8_t> hs(b.s_size);  // the scales copied back for fold_ok (outlives the staging)
+  Staging stage(st);                  // every return below synchronises, then frees
+  if (!stage.alloc(cz + qz + sz + zz + rz)) return staging_finish("nad_device_quantize", stage);
+  int8_t* dcodes = reinterpret_cast<int8_t*>(stage.ptr());
+  uint8_t* dq = stage.ptr() + cz;
   uint8_t* ds = dq + qz;
   int8_t* dz = b.asym ? reinterpret_cast<int8_t*>(ds + sz) : nullptr;
   uint16_t* dr = b.has_reduce ? reinterpret_cast<uint16_t*>(ds + sz + zz) : nullptr;
@@ -209,7 +203,6 @@ extern "C" int nad_device_quantize(const void* wsrc, int w_dtype, int n, int k, 
   if (repack_sections(b, w, dq, ds, dz, st)) return -1;
 
   // fold_ok by the rule of the load, over the small scale buffer copied back
-  std::vector<uint8_t> hs(b.s_size);
   HIP_OK(hipMemcpyAsync(hs.data(), ds, b.s_size, hipMemcpyDeviceToHost, st));
   if (blob_out) {
     nad_host_cache_evict(blob_out);  // a pack entry is about to rewrite this blob
@@ -220,12 +213,10 @@ extern "C" int nad_device_quantize(const void* wsrc, int w_dtype, int n, int k, 
     if (b.asym) HIP_OK(hipMemcpyAsync(hb + b.z_off, dz, b.z_size, hipMemcpyDeviceToHost, st));
     if (b.has_reduce) HIP_OK(hipMemcpyAsync(hb + b.r_off, dr, b.r_size, hipMemcpyDeviceToHost, st));
   }
-  HIP_OK(hipStreamSynchronize(st));
+  if (staging_finish("nad_device_quantize", stage)) return -1;
   Blob sb = b;  // the scales alone: Blob::scale_at reads base + s_off
   sb.s_off = 0;
   w.fold_ok = blob_fold_ok(sb, hs.data(), w.bits) ? 1 : 0;
-  HIP_OK(hipFree(stage.p));
-  stage.p = nullptr;
   std::memcpy(devstor, &w, sizeof(w));
   return 0;
 }

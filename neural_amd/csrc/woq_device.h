@@ -175,6 +175,19 @@ static __constant__ _Float16 kF4LutH[3][16] = {
      _Float16(0.33791524171829224f), _Float16(0.44070982933044434f), _Float16(0.5626170039176941f),
      _Float16(0.7229568362236023f), _Float16(1.0f)}};
 
+// the same values in fp32, for the kernels that dequantize to fp32 (nad_unrepack_kernel, woq_get_rows_kernel)
+static __constant__ float kF4LutF[3][16] = {
+    {0.00000000f, 5.208333333e-03f, 0.66666667f, 1.00000000f, 0.33333333f, 0.50000000f, 0.16666667f, 0.25000000f,
+     -1.f * 0.00000000f, -1.f * 5.208333333e-03f, -1.f * 0.66666667f, -1.f * 1.00000000f, -1.f * 0.33333333f,
+     -1.f * 0.50000000f, -1.f * 0.16666667f, -1.f * 0.25000000f},
+    {0.f, 0.010416666666666666f, 0.16666666666666666f, 0.25f, 0.333333333333333f, 0.5f, 0.6666666666666f, 1.f,
+     -1.f * 0.f, -1.f * 0.010416666666666666f, -1.f * 0.16666666666666666f, -1.f * 0.25f, -1.f * 0.333333333333333f,
+     -1.f * 0.5f, -1.f * 0.6666666666666f, -1.f * 1.f},
+    {0.f, -0.6961928009986877f, -0.5250730514526367f, -0.39491748809814453f, -0.28444138169288635f,
+     -0.18477343022823334f, -0.09105003625154495f, -1.f, 0.07958029955625534f, 0.16093020141124725f,
+     0.24611230194568634f, 0.33791524171829224f, 0.44070982933044434f, 0.5626170039176941f, 0.7229568362236023f,
+     1.0f}};
+
 // the 16 fp16 LUT entries as byte planes: lo[i] holds the low bytes of entries 4i..4i+3, hi[i] the high bytes
 struct F4Lut {
   uint32_t lo[4], hi[4];

@@ -2,16 +2,17 @@
 //
 // A Q4_0 row is K/32 blocks {fp16 d; u8 qs[16]} (neural_speed/core/data_types.h:79-83), value = (nibble - 8) * d with
 // element j < 16 in the low nibble of qs[j] and j >= 16 in the high nibble of qs[j - 16] (vectors/cpu/quantize.h:
-// 686-704).  That is exactly a symmetric int4, group-32, fp16-scale weight, so nad_q4_0_repack_kernel writes it into
+// 686-704).  That is exactly a symmetric int4, group-32, fp16-scale weight, so nad_gguf_repack_kernel<2> writes it into
 // the same MFMA tile layout as a BTLA blob (woq_layout.h) and every forward kernel serves it unchanged.
 //
 // The reference multiplies a Q4_0 matrix by quantizing the activation rows to Q8_0 (vec_dot_type, ne_layers.c:266-273;
 // quantize_row_q8_0_reference, quantize.h:422-445) and summing per block sumi * d_w * d_a (vec_dot.h:187-204).
-// nad_q8_0_quant_kernel is that quantizer; woq_i8.hip's GEMM runs the block dot products in its signed-activation mode.
+// nad_q8_quant_kernel<AT, false> is that quantizer (<AT, true>: the Q8_1 rows of Q4_1 / Q5_1); woq_i8.hip's GEMM runs
+// the block dot products in its signed-activation mode.
 //
 // The other four legacy block types (data_types.h:85-118, dequantize_row_*: quantize.h:706-796) land in the same
-// layouts: Q8_0 and Q5_0 as symmetric int8 (q + 128), Q5_1 as int8 with the true q in 0..31 (q + 128), Q4_1 as
-// symmetric int4.  The symmetric nibble decodes as nibble - 8, and Q4_1's q in 0..15 plus 8 does not fit a nibble: the
+// layouts through the same kernel template, each described by its row of kGgufTypes (woq_gguf.h): Q8_0 and Q5_0 as
+// symmetric int8 (q + 128), Q5_1 as int8 with the true q in 0..31 (q + 128), Q4_1 as symmetric int4.  The symmetric nibble decodes as nibble - 8, and Q4_1's q in 0..15 plus 8 does not fit a nibble: the
 // nibble holds q itself, the kernels see q - 8, and w = (q - 8) d + (8 d + m).  (An asymmetric layout with zero point
 // -8 would decode q, but the stripe-stream GEMV does not take asymmetric groups of 32.)  The fp16 block minimum of
 // Q4_1 / Q5_1 goes into the descriptor's mins region untouched: m / d is no integer, so it cannot ride in a zero point.
@@ -31,104 +32,45 @@
 
 namespace nad {
 
-// one thread per (row n, block b): 18 bytes in, four dwords of the tile + one fp16 scale out
-__global__ void nad_q4_0_repack_kernel(const uint8_t* __restrict__ src, int n, int k, DeviceWeight w) {
-  const int nb = k / 32;
-  const int64_t idx = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (idx >= int64_t(n) * nb) return;
-  const int row = int(idx / nb), b = int(idx % nb);
-  const uint8_t* blk = src + (size_t(row) * nb + b) * 18;
-  uint8_t qs[16];
-#pragma unroll
-  for (int j = 0; j < 16; j++) qs[j] = blk[2 + j];
-  const int s = row >> 4, nl = row & 15;
-  const int t = b >> 2, d = b & 3;
-  uint32_t* tiles = static_cast<uint32_t*>(w.tiles);
-#pragma unroll
-  for (int kq = 0; kq < 4; kq++) {
-    uint32_t word = 0;
-#pragma unroll
-    for (int e = 0; e < 8; e++) {
-      const int j = kq * 8 + e;
-      const uint32_t nib = j < 16 ? (qs[j] & 15u) : (qs[j - 16] >> 4);
-      const int p = (e & 1) ? 4 + (e >> 1) : (e >> 1);  // woq_layout.h int4 element order
-      word |= nib << (4 * p);
-    }
-    tiles[(tile_index(w.kmajor, w.ns, w.nt, s, t) * 64 + kq * 16 + nl) * 4 + d] = word;
-  }
-  uint16_t dh = uint16_t(blk[0]) | (uint16_t(blk[1]) << 8);
-  static_cast<uint16_t*>(w.scales)[scale_row(w.kmajor, w.ns, w.ng, s, b) * 16 + nl] = dh;
-}
-
-// quantize_row_q8_0_reference: per (row, 32-block) amax, d = amax / 127, q = roundf(x / d) (x * (1 / d)), d kept fp16
-template <int AT>
-__global__ __launch_bounds__(256) void nad_q8_0_quant_kernel(Q80Args a) {
-  const int nb = a.K / 32;
-  const int64_t idx = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (idx >= int64_t(a.M) * nb) return;
-  const int row = int(idx / nb), b = int(idx % nb);
-  const size_t rb = size_t(row) * a.lda + size_t(b) * 32;
-  float x[32];
-  float amax = 0.0f;
-#pragma unroll
-  for (int j = 0; j < 32; j++) {
-    x[j] = a_elem<AT>(a.A, rb + j);
-    const float v = fabsf(x[j]);
-    amax = amax > v ? amax : v;  // MAX(amax, fabsf(v))
-  }
-  const float d = amax / 127.f;
-  const float id = d != 0.f ? 1.0f / d : 0.0f;
-  const __half dh = __float2half_rn(d);
-  const float dy = __half2float(dh);
-  int8_t* out = a.blocks ? a.blocks + (size_t(row) * nb + b) * 34 : nullptr;
-  if (out) {
-    const uint16_t bits = __half_as_ushort(dh);
-    out[0] = int8_t(bits & 0xff);
-    out[1] = int8_t(bits >> 8);
-  }
-#pragma unroll
-  for (int j = 0; j < 32; j++) {
-    const int8_t q = int8_t(int(roundf(x[j] * id)));
-    if (a.aq) a.aq[size_t(row) * a.ldq + b * 32 + j] = q;
-    if (out) out[2 + j] = q;
-  }
-  if (a.aq && b == nb - 1)
-    for (int k = a.K; k < a.kp; k++) a.aq[size_t(row) * a.ldq + k] = 0;
-  if (a.sa) a.sa[size_t(row) * nb + b] = make_float2(dy, 0.f);
-}
-
-// ---------------------------------------------------------------------------------------- Q4_1 / Q5_0 / Q5_1 / Q8_0
-// one thread per (row n, block b) of a GGUF matrix: the 32 stored values into the tile, the fp16 scale (and min) as is
+// ---------------------------------------------------------------------------------------- the 32-element block types
+// one thread per (row n, block b) of a GGUF matrix: the 32 stored values into the tile, the fp16 scale (and min) as is.
+// TYPE's row of kGgufTypes (woq_gguf.h) gives the block's shape and what a code means
 template <int TYPE>
 __global__ void nad_gguf_repack_kernel(const uint8_t* __restrict__ src, int n, int k, DeviceWeight w) {
-  constexpr int BB = TYPE == 3 ? 20 : (TYPE == 6 ? 22 : (TYPE == 7 ? 24 : 34));  // block bytes
-  constexpr bool HAS_M = TYPE == 3 || TYPE == 7;
-  constexpr int QS = HAS_M ? 4 : 2;  // offset of qh (5-bit types) or qs
+  constexpr GgufType T = *gguf_type_by_id(TYPE);
+  constexpr int BB = T.block_bytes;
+  constexpr bool HAS_M = T.has_min;
+  constexpr int QS = HAS_M ? 4 : 2;                 // offset of qh (5-bit types) or qs
+  constexpr int CODE_BITS = (BB - QS) * 8 / 32;     // 4, 5 (16 bytes of nibbles behind the 32 high bits) or 8
+  // stored value = code + ADD: the layout decodes stored - (8 | 128), the type code - code_zero (Q4_0: nibble; Q4_1:
+  // (q - 8) + 8; Q5_0: (q - 16) + 128; Q5_1: q + 128)
+  constexpr uint32_t ADD = (T.bits == 4 ? 8 : 128) - T.min_bias - T.code_zero;
+  static_assert(T.block_elems == 32 && (T.bits == 4 || T.bits == 8), "a 32-element type in the int4 / int8 layout");
   const int nb = k / 32;
   const int64_t idx = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
   if (idx >= int64_t(n) * nb) return;
   const int row = int(idx / nb), b = int(idx % nb);
   const uint8_t* blk = src + (size_t(row) * nb + b) * BB;
   uint32_t v[32];  // the stored value of element j
-  if constexpr (TYPE == 8) {
+  if constexpr (CODE_BITS == 8) {
 #pragma unroll
     for (int j = 0; j < 32; j++) v[j] = uint32_t(blk[2 + j]) ^ 0x80u;  // s8 q -> q + 128
   } else {
     uint32_t qh = 0;
     const uint8_t* qs = blk + QS;
-    if constexpr (TYPE == 6 || TYPE == 7) {
+    if constexpr (CODE_BITS == 5) {
       qh = uint32_t(qs[0]) | (uint32_t(qs[1]) << 8) | (uint32_t(qs[2]) << 16) | (uint32_t(qs[3]) << 24);
       qs += 4;
     }
 #pragma unroll
     for (int j = 0; j < 32; j++) {
       const uint32_t q = (j < 16 ? (qs[j] & 15u) : (qs[j - 16] >> 4)) | (((qh >> j) & 1u) << 4);
-      v[j] = TYPE == 3 ? q : (TYPE == 6 ? q + 112u : q + 128u);  // Q4_1: (q - 8) + 8; Q5_0: (q - 16) + 128; Q5_1: q + 128
+      v[j] = q + ADD;
     }
   }
   const int s = row >> 4, nl = row & 15;
   uint32_t* tiles = static_cast<uint32_t*>(w.tiles);
-  if constexpr (TYPE == 3) {  // int4 layout: four blocks per tile, one dword per k-quarter
+  if constexpr (T.bits == 4) {  // int4 layout: four blocks per tile, one dword per k-quarter
     const int t = b >> 2, d = b & 3;
 #pragma unroll
     for (int kq = 0; kq < 4; kq++) {
@@ -156,9 +98,12 @@ __global__ void nad_gguf_repack_kernel(const uint8_t* __restrict__ src, int n, i
   if constexpr (HAS_M) static_cast<uint16_t*>(w.mins)[si] = uint16_t(blk[2]) | (uint16_t(blk[3]) << 8);
 }
 
-// quantize_row_q8_1_reference (quantize.h:546-579): d = amax / 127 kept fp32, q = roundf(x * (1 / d)), s = sum(q) * d
-template <int AT>
-__global__ __launch_bounds__(256) void nad_q8_1_quant_kernel(Q81Args a) {
+// ---------------------------------------------------------------------------------------- Q8_0 / Q8_1 activation rows
+// per (row, 32-block): amax, d = amax / 127, q = roundf(x * (1 / d)).  Q8_0 (quantize_row_q8_0_reference, quantize.h:
+// 422-445) keeps d as fp16 in blocks of 34 bytes; Q8_1 (quantize_row_q8_1_reference, quantize.h:546-579) keeps d fp32
+// and adds s = sum(q) * d, blocks of 40 bytes
+template <int AT, bool Q81>
+__global__ __launch_bounds__(256) void nad_q8_quant_kernel(Q8Args a) {
   const int nb = a.K / 32;
   const int64_t idx = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
   if (idx >= int64_t(a.M) * nb) return;
@@ -170,27 +115,39 @@ __global__ __launch_bounds__(256) void nad_q8_1_quant_kernel(Q81Args a) {
   for (int j = 0; j < 32; j++) {
     x[j] = a_elem<AT>(a.A, rb + j);
     const float v = fabsf(x[j]);
-    amax = amax > v ? amax : v;
+    amax = amax > v ? amax : v;  // MAX(amax, fabsf(v))
   }
   const float d = amax / 127.f;
   const float id = d != 0.f ? 1.0f / d : 0.0f;
-  int8_t* out = a.blocks ? a.blocks + (size_t(row) * nb + b) * 40 : nullptr;
+  constexpr int BB = Q81 ? 40 : 34, QS = BB - 32;  // block bytes, offset of the codes
+  const __half dh = __float2half_rn(d);
+  const float dk = Q81 ? d : __half2float(dh);  // the d the block keeps
+  int8_t* out = a.blocks ? a.blocks + (size_t(row) * nb + b) * BB : nullptr;
+  if constexpr (!Q81) {
+    if (out) {
+      const uint16_t bits = __half_as_ushort(dh);
+      out[0] = int8_t(bits & 0xff);
+      out[1] = int8_t(bits >> 8);
+    }
+  }
   int sum = 0;
 #pragma unroll
   for (int j = 0; j < 32; j++) {
     const int8_t q = int8_t(int(roundf(x[j] * id)));
     sum += q;
     if (a.aq) a.aq[size_t(row) * a.ldq + b * 32 + j] = q;
-    if (out) out[8 + j] = q;
+    if (out) out[QS + j] = q;
   }
-  const float sd = float(sum) * d;
-  if (out) {
-    reinterpret_cast<float*>(out)[0] = d;  // blocks are 40 bytes: 4-byte aligned with the buffer
-    reinterpret_cast<float*>(out)[1] = sd;
+  const float sd = Q81 ? float(sum) * d : 0.f;
+  if constexpr (Q81) {
+    if (out) {
+      reinterpret_cast<float*>(out)[0] = d;  // blocks are 40 bytes: 4-byte aligned with the buffer
+      reinterpret_cast<float*>(out)[1] = sd;
+    }
   }
   if (a.aq && b == nb - 1)
     for (int k = a.K; k < a.kp; k++) a.aq[size_t(row) * a.ldq + k] = 0;
-  if (a.sa) a.sa[size_t(row) * nb + b] = make_float2(d, sd);
+  if (a.sa) a.sa[size_t(row) * nb + b] = make_float2(dk, sd);
 }
 
 // ---------------------------------------------------------------------------------------- the minimum term
@@ -352,28 +309,36 @@ __global__ __launch_bounds__(256) void woq_min_term_tiled_kernel(MinTermArgs a) 
 hipError_t launch_gguf_repack(int type, const uint8_t* src, int n, int k, const DeviceWeight& w, hipStream_t st) {
   const int64_t total = int64_t(n) * (k / 32);
   const dim3 grid(int((total + 255) / 256));
-  if (type == 3)
-    hipLaunchKernelGGL(nad_gguf_repack_kernel<3>, grid, dim3(256), 0, st, src, n, k, w);
-  else if (type == 6)
-    hipLaunchKernelGGL(nad_gguf_repack_kernel<6>, grid, dim3(256), 0, st, src, n, k, w);
-  else if (type == 7)
-    hipLaunchKernelGGL(nad_gguf_repack_kernel<7>, grid, dim3(256), 0, st, src, n, k, w);
-  else if (type == 8)
-    hipLaunchKernelGGL(nad_gguf_repack_kernel<8>, grid, dim3(256), 0, st, src, n, k, w);
-  else
-    return hipErrorInvalidValue;
+  switch (type) {
+#define NAD_REPACK(T) \
+  case T: hipLaunchKernelGGL(nad_gguf_repack_kernel<T>, grid, dim3(256), 0, st, src, n, k, w); break
+    NAD_REPACK(2);
+    NAD_REPACK(3);
+    NAD_REPACK(6);
+    NAD_REPACK(7);
+    NAD_REPACK(8);
+#undef NAD_REPACK
+    default: return hipErrorInvalidValue;
+  }
   return hipGetLastError();
 }
 
-hipError_t launch_q8_1_quant(const Q81Args& a, int act_t, hipStream_t st) {
+template <bool Q81>
+static void launch_q8_quant_t(const Q8Args& a, int act_t, dim3 grid, hipStream_t st) {
+  if (act_t == kActF32)
+    hipLaunchKernelGGL((nad_q8_quant_kernel<kActF32, Q81>), grid, dim3(256), 0, st, a);
+  else if (act_t == kActF16)
+    hipLaunchKernelGGL((nad_q8_quant_kernel<kActF16, Q81>), grid, dim3(256), 0, st, a);
+  else
+    hipLaunchKernelGGL((nad_q8_quant_kernel<kActBF16, Q81>), grid, dim3(256), 0, st, a);
+}
+hipError_t launch_q8_quant(const Q8Args& a, bool q8_1, int act_t, hipStream_t st) {
   const int64_t total = int64_t(a.M) * (a.K / 32);
   const dim3 grid(int((total + 255) / 256));
-  if (act_t == kActF32)
-    hipLaunchKernelGGL(nad_q8_1_quant_kernel<kActF32>, grid, dim3(256), 0, st, a);
-  else if (act_t == kActF16)
-    hipLaunchKernelGGL(nad_q8_1_quant_kernel<kActF16>, grid, dim3(256), 0, st, a);
+  if (q8_1)
+    launch_q8_quant_t<true>(a, act_t, grid, st);
   else
-    hipLaunchKernelGGL(nad_q8_1_quant_kernel<kActBF16>, grid, dim3(256), 0, st, a);
+    launch_q8_quant_t<false>(a, act_t, grid, st);
   return hipGetLastError();
 }
 
@@ -414,24 +379,6 @@ hipError_t launch_min_term_tiled(const MinTermArgs& a, hipStream_t st) {
   if (a.mins && !a.S) return hipErrorInvalidValue;
   const dim3 grid((a.g.w.n + 63) / 64, (a.M + 63) / 64);
   hipLaunchKernelGGL(woq_min_term_tiled_kernel, grid, dim3(256), 0, st, a);
-  return hipGetLastError();
-}
-
-hipError_t launch_q4_0_repack(const uint8_t* src, int n, int k, const DeviceWeight& w, hipStream_t st) {
-  const int64_t total = int64_t(n) * (k / 32);
-  hipLaunchKernelGGL(nad_q4_0_repack_kernel, dim3(int((total + 255) / 256)), dim3(256), 0, st, src, n, k, w);
-  return hipGetLastError();
-}
-
-hipError_t launch_q8_0_quant(const Q80Args& a, int act_t, hipStream_t st) {
-  const int64_t total = int64_t(a.M) * (a.K / 32);
-  const dim3 grid(int((total + 255) / 256));
-  if (act_t == kActF32)
-    hipLaunchKernelGGL(nad_q8_0_quant_kernel<kActF32>, grid, dim3(256), 0, st, a);
-  else if (act_t == kActF16)
-    hipLaunchKernelGGL(nad_q8_0_quant_kernel<kActF16>, grid, dim3(256), 0, st, a);
-  else
-    hipLaunchKernelGGL(nad_q8_0_quant_kernel<kActBF16>, grid, dim3(256), 0, st, a);
   return hipGetLastError();
 }
 

@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <cstdint>
 
+#include "woq_gguf.h"
 #include "woq_layout.h"
 
 namespace nad {
@@ -333,18 +334,16 @@ struct I8Args {
   int ld_aux;
   SkinnyWeight w;
 };
-// GGUF Q4_0 weights / Q8_0 activations (woq_gguf.hip)
-struct Q80Args {
+// GGUF Q8_0 / Q8_1 activation rows (woq_gguf.hip).  Q8_0: sa = {float(fp16 d), 0}, raw blocks {fp16 d; int8 qs[32]}
+// (34 bytes); Q8_1: d kept fp32, sa = {d, float(sum q) * d}, raw blocks {float d; float s; int8 qs[32]} (40 bytes)
+struct Q8Args {
   const void* A;
   int lda, M, K;        // K % 32 == 0
   int8_t* aq;           // [M][ldq] s8 codes, zero in [K, kp)
   int ldq, kp;
-  float2* sa;           // [M][K/32] {float(fp16 d), 0}
-  int8_t* blocks;       // optional raw block_q8_0 rows [M][K/32][34]
+  float2* sa;           // [M][K/32]
+  int8_t* blocks;       // optional raw block rows [M][K/32][34 | 40]
 };
-// Q8_1 activations (quantize_row_q8_1_reference): as Q80Args with d kept fp32, sa = {d, float(sum q) * d} and raw
-// blocks {float d; float s; int8 qs[32]} (40 bytes)
-typedef Q80Args Q81Args;
 // The minimum term of GGUF Q4_1 / Q5_1 (woq_gguf.hip): out[m][n] = epi(out[m][n] + sum_b S[m][b] * mins[n][b]), S the
 // block sums of the activations (S null: woq_min_term_kernel sums A itself).  g carries the epilogue operands and the
 // output (g.w.out / ldo / n / bias, g.epi, g.res, g.aux) for gemm_epilogue4; mins null = the epilogue alone.
@@ -362,15 +361,14 @@ struct MinTermArgs {
 };
 constexpr int kMinTermSmallM = 16;          // woq_min_term_kernel: rows it takes ...
 constexpr size_t kMinTermSmallLds = 65536;  // ... while M * K/32 floats fit this much LDS
-hipError_t launch_q4_0_repack(const uint8_t* src, int n, int k, const DeviceWeight& w, hipStream_t stream);
-// type: the GGUF type (3 Q4_1, 6 Q5_0, 7 Q5_1, 8 Q8_0); src: n rows of k/32 blocks on the device
+// type: a 32-element GGUF type of woq_gguf.h (2 Q4_0, 3 Q4_1, 6 Q5_0, 7 Q5_1, 8 Q8_0); src: n rows of k/32 blocks on
+// the device
 hipError_t launch_gguf_repack(int type, const uint8_t* src, int n, int k, const DeviceWeight& w, hipStream_t stream);
-hipError_t launch_q8_1_quant(const Q81Args& a, int act_t, hipStream_t stream);
+hipError_t launch_q8_quant(const Q8Args& a, bool q8_1, int act_t, hipStream_t stream);
 // block sums of the activation rows into S[m * ng + b] (the pre-pass of launch_min_term_tiled)
 hipError_t launch_block_sums(const void* A, int act_t, int lda, int M, int K, float* S, hipStream_t stream);
 hipError_t launch_min_term(const MinTermArgs& a, int act_t, hipStream_t stream);        // M <= kMinTermSmallM
 hipError_t launch_min_term_tiled(const MinTermArgs& a, hipStream_t stream);            // any M, S given
-hipError_t launch_q8_0_quant(const Q80Args& a, int act_t, hipStream_t stream);
 // GGUF Q6_K (woq_q6k.hip; the layout: woq_layout.h).  src: n rows of k/256 block_q6_K on the device
 hipError_t launch_q6k_repack(const uint8_t* src, int n, int k, const DeviceWeight& w, hipStream_t stream);
 // (d * sc) * q in fp32, [K][N]

@@ -82,7 +82,7 @@ struct DeviceWeight {
   int32_t fold_ok;    // every (q - zp) * scale of the weight is 0 or an fp16 normal: the prefill GEMMs may fold the
                       // group scale into the fp16 B fragment (checked at load)
   void* mins;         // fp16 block mins of GGUF Q4_1 / Q5_1 (nullptr: the weight has none); the GGUF type itself is
-                      // tagged in src_core_id (capi_internal.h kGguf*)
+                      // tagged in src_core_id (woq_gguf.h kGguf*)
   int32_t min_bias;   // with mins: the layout decodes q - min_bias (8 for Q4_1, whose q in 0..15 is stored as the
                       // nibble itself; 0 for Q5_1), so w = decoded * d + (min_bias * d + m) -- both products exact
 };

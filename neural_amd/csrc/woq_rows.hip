@@ -27,19 +27,6 @@
 
 namespace nad {
 
-// the fp32 values of the F4 codes (bestla_utils.h:749-790): the literals of nad_unrepack_kernel's table
-static __constant__ float kRowsF4Lut[3][16] = {
-    {0.00000000f, 5.208333333e-03f, 0.66666667f, 1.00000000f, 0.33333333f, 0.50000000f, 0.16666667f, 0.25000000f,
-     -1.f * 0.00000000f, -1.f * 5.208333333e-03f, -1.f * 0.66666667f, -1.f * 1.00000000f, -1.f * 0.33333333f,
-     -1.f * 0.50000000f, -1.f * 0.16666667f, -1.f * 0.25000000f},
-    {0.f, 0.010416666666666666f, 0.16666666666666666f, 0.25f, 0.333333333333333f, 0.5f, 0.6666666666666f, 1.f,
-     -1.f * 0.f, -1.f * 0.010416666666666666f, -1.f * 0.16666666666666666f, -1.f * 0.25f, -1.f * 0.333333333333333f,
-     -1.f * 0.5f, -1.f * 0.6666666666666f, -1.f * 1.f},
-    {0.f, -0.6961928009986877f, -0.5250730514526367f, -0.39491748809814453f, -0.28444138169288635f,
-     -0.18477343022823334f, -0.09105003625154495f, -1.f, 0.07958029955625534f, 0.16093020141124725f,
-     0.24611230194568634f, 0.33791524171829224f, 0.44070982933044434f, 0.5626170039176941f, 0.7229568362236023f,
-     1.0f}};
-
 // fp32 -> the 16 bits of the output type, round to nearest even (NaN: the quiet NaN torch writes)
 template <int OT>
 __device__ __forceinline__ uint32_t rows_cvt16(float x) {
@@ -153,7 +140,7 @@ __global__ __launch_bounds__(kRowsWaves * 64) void woq_get_rows_kernel(GetRowsAr
             const uint32_t e = ((code & 0x7f) >> mb) - (1u << (eb - 1)) + 128;
             q = __uint_as_float(((code & 0x80) << 24) | (e << 23) | ((code << (23 - mb)) & 0x7fffffu));
           } else if constexpr (KIND == 1) {
-            q = kRowsF4Lut[w.f4kind][code & 15];
+            q = kF4LutF[w.f4kind][code & 15];
           } else {
             q = float(int(code) - BIAS - zp);
           }

@@ -10,6 +10,11 @@ the entry's time comes from a kernel trace of this tool (--no-host keeps the tra
 
 Usage: python tools/quantize_times.py [--shapes 4096x4096;11008x4096;4096x11008;32000x4096] [--group 128]
            [--weight int4] [--scale fp16] [--act fp16] [--rounds 7] [--host-rounds 3] [--threads 16] [--no-host]
+
+--host-load times the two host load entries alone, per shape: nad_device_load of the packed blob and
+nad_gguf_device_load of a Q4_1 matrix of the same shape (stage, repack, synchronise, free; --rounds calls each).  To
+compare two builds, run it once per build with NAD_LIB_PATH, alternating, and read the difference against the spread
+the same build shows between its own runs.
 """
 import argparse
 import os
@@ -38,6 +43,21 @@ def cell(v):
     return f"{statistics.median(v):10.3f} ({min(v):.3f} .. {max(v):.3f})"
 
 
+def host_load(args, np, bestla, sync):
+    print(f"library {os.path.basename(bestla.lib()._name)}; ms per call, median (min .. max) of {args.rounds} calls")
+    print(f"{'N x K':<14}{'nad_device_load ms':>34}{'nad_gguf_device_load Q4_1 ms':>36}")
+    for shape in args.shapes.split(";"):
+        n, k = (int(v) for v in shape.split("x"))
+        rng = np.random.default_rng(n + k)
+        blob = bestla.quantize(rng.standard_normal((n, k), dtype=np.float32), group_size=args.group,
+                               weight_dtype=args.weight, scale_dtype=args.scale)
+        blocks = rng.integers(0, 256, size=(n * (k // 32), 20), dtype=np.uint8)  # block_q4_1: fp16 d, fp16 m, 16 bytes
+        blocks[:, 0:4] = rng.uniform(1e-3, 1e-2, (n * (k // 32), 2)).astype(np.float16).view(np.uint8)
+        t_blob = timed(lambda: bestla.DeviceWeight(blob), args.rounds, sync)
+        t_gguf = timed(lambda: bestla.DeviceWeight.from_gguf(bestla.GGUF_Q4_1, blocks, n, k), args.rounds, sync)
+        print(f"{shape:<14}{cell(t_blob):>34}{cell(t_gguf):>36}", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default="4096x4096;11008x4096;4096x11008;32000x4096", help="NxK;NxK;...")
@@ -49,6 +69,7 @@ def main():
     ap.add_argument("--host-rounds", type=int, default=3)
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--no-host", action="store_true")
+    ap.add_argument("--host-load", action="store_true", help="time nad_device_load and nad_gguf_device_load (Q4_1) only")
     args = ap.parse_args()
     os.environ["NAD_HOST_THREADS"] = str(args.threads)
     import numpy as np
@@ -58,6 +79,8 @@ def main():
     esz = 4 if args.act == "fp32" else 2
     kw = dict(group_size=args.group, weight_dtype=args.weight, scale_dtype=args.scale)
     sync = torch.cuda.synchronize
+    if args.host_load:
+        return host_load(args, np, bestla, sync)
     print(f"{torch.cuda.get_device_name()}  {args.weight} g{args.group}, {args.scale} scales, {args.act} input; ms per "
           f"call, median (min .. max) of {args.rounds} device / {args.host_rounds} host calls; host path on "
           f"{args.threads} threads")
