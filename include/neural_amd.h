@@ -201,8 +201,8 @@ int nad_device_forward(const void* act, int act_dtype, const void* devstor, floa
  * workspace sizing -- with every launch recorded instead of issued; no device memory is touched and no GPU is needed.
  * out (versioned by nout): [kernel NAD_KERNEL_*, grid, threads per workgroup, split-K runs, flags (bit 0: scale folded
  * into the fp16 weights; bit 1: gemm4 waves split over K; bit 2: the M = 1 decode launch takes the specialised
- * woq_gemv_m1s_kernel, see NAD_GEMV_M1_SPEC), launches including pre-passes].  Returns the number of values
- * written or -1. */
+ * woq_gemv_m1s_kernel, see NAD_GEMV_M1_SPEC; bit 3: ... in its load-ahead order, see NAD_GEMV_AHEAD), launches
+ * including pre-passes].  Returns the number of values written or -1. */
 #define NAD_KERNEL_GEMV_M1 1   /* woq_gemv_m1_kernel: M = 1 decode */
 #define NAD_KERNEL_GEMV 2      /* woq_gemv_kernel: the stripe-stream GEMV, M <= 16 */
 #define NAD_KERNEL_SKINNY 3    /* woq_skinny_kernel: decode geometries the stream does not take */
@@ -233,6 +233,12 @@ int nad_plan_weight(const void* devstor, int m, int act_dtype, int64_t* out, int
 int nad_plan_qkv_forward(int bits, int nq, int nk, int nv, int k, int blocksize, int scale_t, int asym, int m,
                          int act_dtype, int64_t* out, int nout);
 int nad_plan_qkv(const void* wq, const void* wk, const void* wv, int m, int act_dtype, int64_t* out, int nout);
+/* Dry runs of nad_device_ffn_gate_up (SiLU * mul, tmp1 given), for two weight geometries of one format (no GPU needed)
+ * and for two weights; out as nad_plan_qkv's.  nad_plan_qkv and nad_plan_gate_up take loaded weights and geometry-only
+ * descriptors (nad_weight_plan_only) alike, so fused calls of mixed formats can be asked without a GPU. */
+int nad_plan_gate_up_forward(int bits, int n, int k, int blocksize, int scale_t, int asym, int m, int act_dtype,
+                             int64_t* out, int nout);
+int nad_plan_gate_up(const void* w1, const void* w3, int m, int act_dtype, int64_t* out, int nout);
 /* fused Q/K/V (ip_fusion_qkv.cpp:22-93): out_i = X . W_i^T, one launch; W_i share K, blocksize, bits, scale dtype */
 int nad_device_qkv_forward(const void* act, int act_dtype, const void* wq, const void* wk, const void* wv, float* oq,
                            float* ok, float* ov, int m, int k, int lda, int ldo_q, int ldo_k, int ldo_v, void* queue);
@@ -418,6 +424,8 @@ typedef struct nad_batch_problem {
 } nad_batch_problem;
 void* nad_batch_create(const nad_batch_problem* problems, int n);
 int nad_batch_run(void* batch, void* queue);
+/* dry run of nad_batch_run: out as nad_plan_forward's (nothing is launched) */
+int nad_plan_batch(void* batch, int64_t* out, int nout);
 void nad_batch_destroy(void* batch);
 
 /* ===== routed expert matmuls: ne_mul_mat_id / ne_mul_id_ffn_silu (neural_speed/core/ne_layers.c:2384-2462, 7783-7916,

@@ -72,6 +72,8 @@ SIGNATURES = {
     "nad_plan_weight": (_i, [_p, _i, _i, _p, _i]),
     "nad_plan_qkv_forward": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _i]),
     "nad_plan_qkv": (_i, [_p, _p, _p, _i, _i, _p, _i]),
+    "nad_plan_gate_up_forward": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _p, _i]),
+    "nad_plan_gate_up": (_i, [_p, _p, _i, _i, _p, _i]),
     "nad_blob_info": (_i, [_p, _p]),
     "nad_device_forward": (_i, [_p, _i, _p, _p, _i, _i, _i, _i, _i, _i, _p, _i, _p, _i, _p]),
     "nad_device_qkv_forward": (_i, [_p, _i, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
@@ -108,6 +110,7 @@ SIGNATURES = {
     "nad_weight_plan_only": (_i, [_i, _i, _i, _i, _i, _i, _i, _p]),
     "nad_batch_create": (_p, [_p, _i]),
     "nad_batch_run": (_i, [_p, _p]),
+    "nad_plan_batch": (_i, [_p, _p, _i]),
     "nad_batch_destroy": (None, [_p]),
     "nad_expert_bank_create": (_p, [_p, _i]),
     "nad_expert_bank_plan_only": (_p, [_p, _i]),

@@ -199,7 +199,8 @@ def plan_forward(bits, n, k, group_size=128, scale_dtype="fp16", asym=False, m=1
 
 def _plan_dict(o):
     return dict(kernel=KERNELS.get(int(o[0]), str(int(o[0]))), grid=int(o[1]), threads=int(o[2]), ksplit=int(o[3]),
-                fold=bool(o[4] & 1), ksw=bool(o[4] & 2), m1_spec=bool(o[4] & 4), launches=int(o[5]))
+                fold=bool(o[4] & 1), ksw=bool(o[4] & 2), m1_spec=bool(o[4] & 4), ahead=bool(o[4] & 8),
+                launches=int(o[5]))
 
 
 def plan_qkv_forward(bits, nq, nk, nv, k, group_size=128, scale_dtype="fp16", asym=False, m=1, act="fp32"):
@@ -214,11 +215,32 @@ def plan_qkv_forward(bits, nq, nk, nv, k, group_size=128, scale_dtype="fp16", as
 
 
 def plan_qkv(wq, wk, wv, m, act="fp32"):
-    """The same dry run for three loaded DeviceWeights (nad_plan_qkv)."""
+    """The same dry run for three DeviceWeights or plan_only_weight descriptors (nad_plan_qkv)."""
     o = np.zeros(6, np.int64)
     at = {"fp32": 0, "fp16": 1, "bf16": 2}[act]
-    if lib().nad_plan_qkv(wq.desc, wk.desc, wv.desc, m, at, _ptr(o), 6) != 6:
+    wq, wk, wv = (getattr(w, "desc", w) for w in (wq, wk, wv))
+    if lib().nad_plan_qkv(wq, wk, wv, m, at, _ptr(o), 6) != 6:
         raise RuntimeError(f"nad_plan_qkv failed: {last_error()}")
+    return _plan_dict(o)
+
+
+def plan_gate_up_forward(bits, n, k, group_size=128, scale_dtype="fp16", asym=False, m=1, act="fp32"):
+    """What the FFN's fused gate/up (SiLU * mul) of two weights of this format launches (nad_plan_gate_up_forward: no
+    GPU needed); the record is plan_qkv_forward's."""
+    o = np.zeros(6, np.int64)
+    st = {"fp32": 0, "bf16": 1, "fp16": 2}[scale_dtype]
+    at = {"fp32": 0, "fp16": 1, "bf16": 2}[act]
+    if lib().nad_plan_gate_up_forward(bits, n, k, group_size, st, int(asym), m, at, _ptr(o), 6) != 6:
+        raise RuntimeError(f"nad_plan_gate_up_forward failed: {last_error()}")
+    return _plan_dict(o)
+
+
+def plan_gate_up(w1, w3, m, act="fp32"):
+    """The same dry run for two loaded DeviceWeights (nad_plan_gate_up)."""
+    o = np.zeros(6, np.int64)
+    at = {"fp32": 0, "fp16": 1, "bf16": 2}[act]
+    if lib().nad_plan_gate_up(w1.desc, w3.desc, m, at, _ptr(o), 6) != 6:
+        raise RuntimeError(f"nad_plan_gate_up failed: {last_error()}")
     return _plan_dict(o)
 
 
@@ -609,6 +631,13 @@ class Batch:
 
     def run(self, stream=None):
         check(lib().nad_batch_run(self.handle, _stream(stream)), "nad_batch_run")
+
+    def plan(self):
+        """what run() launches (nad_plan_batch: a dry run, nothing is launched)"""
+        o = np.zeros(6, np.int64)
+        if lib().nad_plan_batch(self.handle, _ptr(o), 6) != 6:
+            raise RuntimeError(f"nad_plan_batch failed: {last_error()}")
+        return _plan_dict(o)
 
     def __del__(self):
         h = getattr(self, "handle", None)

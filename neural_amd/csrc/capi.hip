@@ -45,6 +45,9 @@ static Knobs read_knobs() {
   // M = 1 launches on woq_gemv_m1s_kernel (compact arguments, weight count / reduce / epilogue at compile time) where
   // one is instantiated; 0: every launch on woq_gemv_m1_kernel with the full GemvArgs (A/B, bit-identity tests)
   k.gemv_m1_spec = env_int("NAD_GEMV_M1_SPEC", 1);
+  // woq_gemv_m1s_kernel's load-ahead order wherever a form is instantiated (QKV, gate/up, one weight of two or more
+  // stages per wave: all measured on, so unset = 1); 0: the present order everywhere (A/B, bit-identity tests)
+  k.gemv_ahead = env_int("NAD_GEMV_AHEAD", 1) != 0;
   k.gemv_dual = env_int("NAD_GEMV_DUAL", 1);  // decode QKV of two formats (int2 Q, K + int4 V) as one launch
   k.gemv_spw = env_int("NAD_GEMV_SPW", 4);
   k.gemv_disable = env_int("NAD_GEMV_DISABLE", 0);

@@ -151,7 +151,7 @@ static int prepare_gemv(GemvArgs& a, int& waves, int& grid, const Act& x, const 
   a.dq_mask = 0x000F000Fu;
   a.dq_magic = 0x64006400u;
   a.m1_nst = kn.gemv_nst;
-  a.m1_spec = kn.gemv_m1_spec;
+  a.m1_spec = kn.gemv_m1_spec ? 1 | (kn.gemv_ahead ? kM1SpecAhead : 0) : 0;
   a.u_q = a.units / grid;
   a.u_r = a.units % grid;
   a.lean = kn.gemv_lean;
@@ -192,7 +192,7 @@ static int try_gemv(const Act& x, const Weights& W, const Epi& e, hipStream_t st
   const int bits = W[0].bits;
   const size_t lds = gemv_lds_layout(a, bits, waves, grid);
   const bool dry = planned(gemv_uses_m1(a, bits, waves) ? NAD_KERNEL_GEMV_M1 : NAD_KERNEL_GEMV, grid, waves * 64, 1,
-                           planning() && gemv_uses_m1s(a, bits, waves) ? 4 : 0);
+                           !planning() ? 0 : (gemv_uses_m1s(a, bits, waves) ? 4 : 0) | (gemv_uses_ahead(a, bits, waves) ? 8 : 0));
   return launch(dry, "gemv kernel", [&] { return launch_gemv(a, bits, waves, grid, lds, st); }) ? 1 : -1;
 }
 
@@ -1036,9 +1036,17 @@ extern "C" int nad_plan_qkv_forward(int bits, int nq, int nk, int nv, int k, int
   return plan_qkv_for(ws, m, act_dtype, out, nout);
 }
 
+// a loaded or a geometry-only (nad_weight_plan_only) weight for the dry runs of fused calls: nothing is launched on it
+static const DeviceWeight* plan_weight(const void* p) {
+  const auto* w = static_cast<const DeviceWeight*>(p);
+  if (w && w->magic == kWeightMagic) return w;
+  set_err("nad_plan_*: weight descriptor is not a neural_amd device weight");
+  return nullptr;
+}
+
 extern "C" int nad_plan_qkv(const void* wq, const void* wk, const void* wv, int m, int act_dtype, int64_t* out,
                             int nout) {
-  const DeviceWeight* ws[3] = {as_weight(wq), as_weight(wk), as_weight(wv)};
+  const DeviceWeight* ws[3] = {plan_weight(wq), plan_weight(wk), plan_weight(wv)};
   if (!ws[0] || !ws[1] || !ws[2]) return -1;
   return plan_qkv_for(ws, m, act_dtype, out, nout);
 }
@@ -1111,6 +1119,52 @@ extern "C" int nad_device_ffn_gate_up(const void* act, int act_dtype, const void
   }
   if (run_gemm(x, *w1, Out{tmp1, fmid}, Epi::gate_of(epi), st, pp)) return -1;
   return run_gemm(x, *w3, up, Epi::mul(tmp1, fmid), st, pp);
+}
+
+// Dry run of nad_device_ffn_gate_up (SiLU * mul, with the tmp1 output): the record is nad_plan_forward's.
+static int plan_gate_up_for(const DeviceWeight& w1, const DeviceWeight& w3, int m, int act_dtype, int64_t* out,
+                            int nout) {
+  if (!out || nout < 0 || m <= 0) {
+    set_err("nad_plan_gate_up*: bad arguments (m=%d)", m);
+    return -1;
+  }
+  NadPlan plan;
+  set_plan(&plan);
+  const void* act = reinterpret_cast<const void*>(uintptr_t(1) << 42);  // aligned, never dereferenced on the host
+  float* t1 = reinterpret_cast<float*>(uintptr_t(1) << 43);
+  float* t2 = reinterpret_cast<float*>((uintptr_t(1) << 43) + (uintptr_t(1) << 38));
+  const int rc = nad_device_ffn_gate_up(act, act_dtype, &w1, &w3, t1, t2, m, w1.k, w1.n, w1.k, kEpiSiluMul, nullptr);
+  set_plan(nullptr);
+  if (rc) return -1;
+  const int64_t v[6] = {plan.kernel, plan.grid, plan.block, plan.ksplit, plan.fold, plan.launches};
+  const int c = nout < 6 ? nout : 6;
+  std::memcpy(out, v, sizeof(int64_t) * size_t(c));
+  return c;
+}
+
+extern "C" int nad_plan_gate_up_forward(int bits, int n, int k, int blocksize, int scale_t, int asym, int m,
+                                        int act_dtype, int64_t* out, int nout) {
+  if ((bits != 2 && bits != 4 && bits != 8) || n <= 0 || k <= 0) {
+    set_err("nad_plan_gate_up_forward: bad arguments (bits=%d n=%d k=%d)", bits, n, k);
+    return -1;
+  }
+  if (blocksize <= 0) blocksize = k;
+  DeviceWeight w[2] = {};
+  for (int i = 0; i < 2; i++) {
+    layout_geometry(w[i], bits, n, k, blocksize, scale_t, asym != 0, false, false);
+    layout_assign(w[i], reinterpret_cast<void*>((uintptr_t(1) << 41) + (uintptr_t(i) << 38)));  // never dereferenced
+    w[i].f4kind = -1;
+    w[i].fold_ok = 1;
+    w[i].owner = nullptr;
+  }
+  return plan_gate_up_for(w[0], w[1], m, act_dtype, out, nout);
+}
+
+extern "C" int nad_plan_gate_up(const void* w1p, const void* w3p, int m, int act_dtype, int64_t* out, int nout) {
+  const DeviceWeight* w1 = plan_weight(w1p);
+  const DeviceWeight* w3 = plan_weight(w3p);
+  if (!w1 || !w3) return -1;
+  return plan_gate_up_for(*w1, *w3, m, act_dtype, out, nout);
 }
 
 int ffn_forward(const void* act, int act_dtype, const void* w1p, const void* w2p, const void* w3p, float* tmp1,
@@ -1256,6 +1310,23 @@ extern "C" int nad_batch_run(void* batch, void* queue) {
          })
              ? 0
              : -1;
+}
+
+// Dry run of nad_batch_run: the record of nad_plan_forward (the batched launch has no specialised or load-ahead form).
+extern "C" int nad_plan_batch(void* batch, int64_t* out, int nout) {
+  if (!batch || !out || nout < 0) {
+    set_err("nad_plan_batch: bad arguments");
+    return -1;
+  }
+  NadPlan plan;
+  set_plan(&plan);
+  const int rc = nad_batch_run(batch, nullptr);
+  set_plan(nullptr);
+  if (rc) return -1;
+  const int64_t v[6] = {plan.kernel, plan.grid, plan.block, plan.ksplit, plan.fold, plan.launches};
+  const int c = nout < 6 ? nout : 6;
+  std::memcpy(out, v, sizeof(int64_t) * size_t(c));
+  return c;
 }
 
 extern "C" void nad_batch_destroy(void* batch) {

@@ -30,7 +30,7 @@ void report(const char* where);
 // Tuning / A-B switches.  Read from the environment ONCE (at the first forward, or by nad_reload_knobs), never per
 // launch: the eager path an NE graph takes (one bestla_device_f32f32_forward per node) must not scan the environment.
 struct Knobs {
-  int gemv_grid, gemv_waves, gemv_lean, gemv_spw, gemv_disable, gemv_dual, gemv_nst, gemv_m1_spec;
+  int gemv_grid, gemv_waves, gemv_lean, gemv_spw, gemv_disable, gemv_dual, gemv_nst, gemv_m1_spec, gemv_ahead;
   int compute_int8;
   int gemm2_disable, gemm4_all, gemm4_disable, ffn_f32, gemm_kernel, gemm7_bm, splitk_disable;
   int gemm3_stagger, gemm4_fold_all, gemm4_fold, gemm4_ksw;

@@ -680,7 +680,7 @@ struct M1General {
   }
 };
 
-template <class P, int BITS, int GPT, int AT, bool ASYM, int KSN, int SPW, int NST, int ST>
+template <class P, int BITS, int GPT, int AT, bool ASYM, int KSN, int SPW, int NST, int ST, bool AHEAD = false>
 __device__ __forceinline__ void m1_stream(const typename P::Args& a, int lane, int wave, int NW, int nsl, int v0,
                                           int nv, bool idle, float* part, int PS) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -762,7 +762,7 @@ __device__ __forceinline__ void m1_stream(const typename P::Args& a, int lane, i
     if (cj >= nv) return;
     const char* ab = abase + cs * slice_step;
 #ifdef NAD_PHASE_TRACE
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if constexpr (!AHEAD) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // AHEAD: waited before the next stage went out
     const unsigned long long tr0 = wall_clock64();
 #endif
     stage_mac<BITS, GPT, ASYM, KSN, ST, false>(S, dq, ab, ab, [](int i) { return i * KT * 2; }, a.scale_t, ssh, acc);
@@ -791,11 +791,34 @@ __device__ __forceinline__ void m1_stream(const typename P::Args& a, int lane, i
     }
   };
 
-  while (cj < nv) {
+  if constexpr (AHEAD) {
+    // Load-ahead order (one register stage, two sets): once the current set has landed, the wave's next live stage is
+    // requested into the other set, and only then is the current one computed -- one live stage outstanding per wave
+    // at any time, nothing requested past the wave's last stage, so the waits are plain vmcnt(0).  The loads sit under
+    // a wave-uniform branch; the scheduling barrier keeps them in front of the stage's first MFMA.
+    static_assert(NST == 1, "the load-ahead order replaces the one-stage loop");
+    StageRegs<GPT, KSN> T;
+    auto ahead = [&](StageRegs<GPT, KSN>& next) {
+      // vmcnt(0) as the builtin, not inline assembly: hipcc then knows that nothing is outstanding here and puts no
+      // wait of its own (which, merged over the branch below, would wait for the loads just issued) before the MFMAs
+      __builtin_amdgcn_s_waitcnt(0x0F70);
+      if (lc.j < nv) P::template load<GPT, ASYM, KSN>(a, next, lc, nv, nsl, wave, NW, v0, lane, vs);
+      __builtin_amdgcn_sched_barrier(0);
+    };
+    while (cj < nv) {
+      ahead(T);
+      compute_stage(S[0]);
+      if (cj >= nv) break;
+      ahead(S[0]);
+      compute_stage(T);
+    }
+  } else {
+    while (cj < nv) {
 #pragma unroll
-    for (int i = 0; i < NST; i++) {
-      compute_stage(S[i]);
-      P::template load<GPT, ASYM, KSN>(a, S[i], lc, nv, nsl, wave, NW, v0, lane, vs);
+      for (int i = 0; i < NST; i++) {
+        compute_stage(S[i]);
+        P::template load<GPT, ASYM, KSN>(a, S[i], lc, nv, nsl, wave, NW, v0, lane, vs);
+      }
     }
   }
 #ifdef NAD_PHASE_TRACE
@@ -1057,7 +1080,7 @@ struct M1Spec {  // m1_stream's policy for woq_gemv_m1s_kernel
 // tail work on, is put together from them and from the remainder r.  Nothing on the way to the first loads of a
 // one-weight or pair launch reads r (the pair's first stage is a gate stripe: weight 0); the 3-weight form's stripe ->
 // weight select does, behind the activation loads.
-template <int BITS, int GPT, int AT, bool ASYM, int KSN, int SPW, int NST, int ST, int NWT, int NSC>
+template <int BITS, int GPT, int AT, bool ASYM, int KSN, int SPW, int NST, int ST, int NWT, int NSC, bool AHEAD = false>
 __global__ __launch_bounds__((m1_max_threads<GPT, KSN>())) void woq_gemv_m1s_kernel(
     const void* A, const void* tiles0, const void* scales0, const void* tiles1, const void* scales1, int a_bytes,
     uint32_t uqr, uint32_t geom, int ns0, GemvM1Rest<NWT> r) {
@@ -1107,7 +1130,7 @@ __global__ __launch_bounds__((m1_max_threads<GPT, KSN>())) void woq_gemv_m1s_ker
   const int v0 = u0 * VPU, nv = nu * VPU;
   const bool idle = NSC == 0 && wave >= nsl;
   float* part = reinterpret_cast<float*>(smem + a.part_off);  // [nv][16 columns][PS]
-  m1_stream<M1Spec<NWT>, BITS, GPT, AT, ASYM, KSN, SPW, NST, ST>(a, lane, wave, NW, nsl, v0, nv, idle, part, PS);
+  m1_stream<M1Spec<NWT>, BITS, GPT, AT, ASYM, KSN, SPW, NST, ST, AHEAD>(a, lane, wave, NW, nsl, v0, nv, idle, part, PS);
 
   // 4) sum each stripe's wave slots in wave order (m1_body's order exactly), then the store
   const int nout = nu * 16;
@@ -1228,13 +1251,13 @@ static bool m1s_packable(const GemvArgs& a, int nwt, int waves) {
   if (a.tpg_shift < 0 || a.tpg_shift > 31 || a.scale_t < 0 || a.scale_t > 3 || waves > 16) return false;
   return nwt != 2 || a.w[0].ns == a.w[1].ns;
 }
-template <int BITS, int GPT, int AT, bool ASYM, int KSN, int SPW, int NST, int ST, int NWT, int NSC>
+template <int BITS, int GPT, int AT, bool ASYM, int KSN, int SPW, int NST, int ST, int NWT, int NSC, bool AHEAD = false>
 static hipError_t m1s_go(const GemvArgs& a, dim3 g, dim3 b, size_t lds, hipStream_t st) {
   const int esz = a.act_t == kActF32 ? 4 : 2;
   const uint32_t uqr = uint32_t(a.u_q) | uint32_t(a.u_r) << 16;
   const uint32_t geom = uint32_t(a.nt) | uint32_t(a.ng) << kM1GeomNgShift | uint32_t(a.tpg_shift) << kM1GeomTpgShift |
                         uint32_t(a.scale_t) << kM1GeomScaleShift | uint32_t(b.x / 64) << kM1GeomWavesShift;
-  return launch_big_lds<woq_gemv_m1s_kernel<BITS, GPT, AT, ASYM, KSN, SPW, NST, ST, NWT, NSC>>(
+  return launch_big_lds<woq_gemv_m1s_kernel<BITS, GPT, AT, ASYM, KSN, SPW, NST, ST, NWT, NSC, AHEAD>>(
       g, b, lds, st, a.A, a.w[0].tiles, a.w[0].scales, NWT > 1 ? a.w[1].tiles : nullptr,
       NWT > 1 ? a.w[1].scales : nullptr, a.K * esz, uqr, geom, a.w[0].ns, m1s_rest<NWT>(a));
 }
@@ -1250,6 +1273,31 @@ static int m1s_nwt(const GemvArgs& a, int waves) {
   }
   return nwt != 0 && m1s_packable(a, nwt, waves) ? nwt : 0;
 }
+// The load-ahead order of m1_stream (AHEAD) exists for the launches of a decode token that run one register stage and
+// stream two or more stages per wave -- int4, one group per tile, fp32 activations, sym and asym:
+//   form 1 / 2 / 3   16 waves of one 2-tile slice each, 1 weight / the {gate, up} pair / 3 weights (fused QKV)
+// in an object of their own (GEMV_PART=6).  The form for Llama's down projection (11 waves of two 4-tile slices) was
+// built and measured and did not gain inside the token: down keeps the present order.
+// m1s_ahead_form: the form that serves the launch, 0 = none, or switched off (NAD_GEMV_AHEAD=0: kM1SpecAhead clear).
+static int m1s_ahead_form(const GemvArgs& a, int bits, int gpt, int waves) {
+  if (bits != 4 || gpt != 1 || a.act_t != kActF32 || !(a.m1_spec & kM1SpecAhead)) return 0;
+  const int ks = lean_ks(a), nwt = m1s_nwt(a, waves);
+  if (nwt == 0 || m1_nst(a, ks, waves) != 1 || m1_stages_per_wave(a, ks, waves) < 2) return 0;
+  const int nsl = (a.nt + ks - 1) / ks;
+  return ks == 2 && waves == 16 && nsl >= 16 ? nwt : 0;
+}
+#if !defined(GEMV_PART) || GEMV_PART == 6
+hipError_t gemv_m1s_ahead_launch(const GemvArgs& a, int form, dim3 g, dim3 b, size_t lds, hipStream_t st) {
+  return by_asym(a, [&](auto as) {
+    constexpr bool AS = as.value;
+    if (form == 1) return m1s_go<4, 1, kActF32, AS, 2, 1, 1, -1, 1, 16, true>(a, g, b, lds, st);
+    if (form == 2) return m1s_go<4, 1, kActF32, AS, 2, 1, 1, -1, 2, 16, true>(a, g, b, lds, st);
+    return m1s_go<4, 1, kActF32, AS, 2, 1, 1, -1, 3, 16, true>(a, g, b, lds, st);
+  });
+}
+#else
+hipError_t gemv_m1s_ahead_launch(const GemvArgs& a, int form, dim3 g, dim3 b, size_t lds, hipStream_t st);
+#endif
 // Instantiated: slices of 1 or 2 tiles, one per wave: every weight count, 16 slots per column or the runtime count,
 // two register stages for one weight only (lm_head); 4-tile slices with fewer than 16 slots per column: two per wave
 // for every weight count (two stages: one weight), four per wave for one weight (the long K of a down projection) --
@@ -1262,6 +1310,10 @@ static bool m1s_launch3(const GemvArgs& a, dim3 g, dim3 b, size_t lds, hipStream
   const int nsl = (a.nt + ks - 1) / ks;
   const bool l16 = waves == 16 && nsl >= 16;
   const int nst = m1_nst(a, ks, waves);
+  if (const int form = m1s_ahead_form(a, BITS, GPT, waves)) {
+    if (e) *e = gemv_m1s_ahead_launch(a, form, g, b, lds, st);
+    return true;
+  }
 #define NAD_M1S(KSN, SPW, NST, NWT, NSC)                                                         \
   do {                                                                                           \
     if (e) *e = m1s_go<BITS, GPT, AT, ASYM, KSN, SPW, NST, ST, NWT, NSC>(a, g, b, lds, st);      \
@@ -1468,6 +1520,12 @@ bool gemv_uses_m1s(const GemvArgs& a, int bits, int waves) {
   if (!lean_ok(a, bits, waves)) return false;
   return bits == 4 ? gemv_m1s_launch_b4(a, gpt, dim3(1), dim3(waves * 64), 0, nullptr, nullptr)
                    : gemv_m1s_launch_b2(a, gpt, dim3(1), dim3(waves * 64), 0, nullptr, nullptr);
+}
+
+bool gemv_uses_ahead(const GemvArgs& a, int bits, int waves) {
+  int tpg = 0;
+  const int gpt = gemv_groups_per_tile(bits, a.nt, a.ng, a.bs, &tpg);
+  return lean_ok(a, bits, waves) && m1s_ahead_form(a, bits, gpt, waves) != 0;
 }
 
 bool gemv_dual_ok(const GemvArgs& a, int bits_a, const GemvArgs& b, int bits_b, int waves) {

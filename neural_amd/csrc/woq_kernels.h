@@ -144,7 +144,11 @@ struct GemvArgs {
   int batch_wpp;              //   reads its activations / weight / output from batch[p]; u_q / u_r split one problem
   int m1_nst;                 // woq_gemv_m1_kernel: register stages in flight per wave (0 = by the stages per wave)
   int m1_spec;                // M = 1 launches may take woq_gemv_m1s_kernel (NAD_GEMV_M1_SPEC; 0: always the kernel above)
+                              //   + kM1SpecAhead: ... in its load-ahead order where a form exists (NAD_GEMV_AHEAD).
+                              //   A host-only bit of this field and not a field of its own: GemvArgs is passed by value
+                              //   to woq_gemv_m1_kernel / woq_gemv_kernel / the dual kernel, whose code must not change
 };
+constexpr int kM1SpecAhead = 2;
 
 // Routed M = 1 launch (woq_gemv_m1_routed_kernel; nad_device_mul_mat_id / nad_device_moe_ffn: ne_mul_mat_id,
 // ne_layers.c:7783-7916).  One expert of a bank: 64 B per entry (one scalar-cache line).
@@ -425,6 +429,8 @@ hipError_t launch_gemv(const GemvArgs& a, int bits, int waves, int grid, size_t 
 bool gemv_uses_m1(const GemvArgs& a, int bits, int waves);
 // ... and would serve it with woq_gemv_m1s_kernel (a.m1_spec, and an instantiation for the launch exists)
 bool gemv_uses_m1s(const GemvArgs& a, int bits, int waves);
+// ... in its load-ahead order (a.m1_spec & kM1SpecAhead, and a form exists for the launch)
+bool gemv_uses_ahead(const GemvArgs& a, int bits, int waves);
 // two M = 1 launches of different formats as one (int2 a + int4 b at groups of 64 or 128, fp32 activations, sym,
 // 16 waves each; a on workgroups [0, ga), b on [ga, ga + gb))
 bool gemv_dual_ok(const GemvArgs& a, int bits_a, const GemvArgs& b, int bits_b, int waves);

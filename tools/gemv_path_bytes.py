@@ -46,12 +46,12 @@ def generic(bits, gpt, at, asym, ksn, spw, batch, nst, st=-1):
         "GemvArgs"
 
 
-def spec(bits, gpt, at, asym, ksn, spw, nst, st, nwt, nsc):
+def spec(bits, gpt, at, asym, ksn, spw, nst, st, nwt, nsc, ahead=False):
     """woq_gemv_m1s_kernel: preloaded leading arguments, weight count / slots per column / epilogue class at compile
-    time."""
+    time; ahead: its load-ahead order."""
     b = lambda v: "true" if v else "false"
-    return "woq_gemv_m1s_kernel<%d,%d,%d,%s,%d,%d,%d,%d,%d,%d>" % (bits, gpt, ACT[at], b(asym), ksn, spw, nst, st, nwt,
-                                                                   nsc), \
+    return "woq_gemv_m1s_kernel<%d,%d,%d,%s,%d,%d,%d,%d,%d,%d%s>" % (bits, gpt, ACT[at], b(asym), ksn, spw, nst, st, nwt,
+                                                                     nsc, ",true" if ahead else ""), \
         "const void*, const void*, const void*, const void*, const void*, int, uint32_t, uint32_t, int, GemvM1Rest<%d>" % nwt
 
 
@@ -73,7 +73,16 @@ def kernel_sets(legacy):
                 ("generic down", generic(4, 1, "f32", False, 4, 2, False, 1))]
     rest += [("asym/bf16-scale (generic)", generic(4, 1, "f32", True, 2, 1, False, 1)),
              ("batched", generic(4, 1, "f32", False, 2, 1, True, 3))]
-    return {"headline": head, "all": head + rest}
+    # the load-ahead forms (GEMV_PART=6), each behind the present form of the same launch
+    ahead = []
+    if not legacy:
+        for label, asym, ksn, spw, nwt, nsc in (("qkv (3 weights)", False, 2, 1, 3, 16), ("gate/up (pair)", False, 2, 1, 2, 16),
+                                                ("one weight", False, 2, 1, 1, 16),
+                                                ("asym qkv", True, 2, 1, 3, 16), ("asym gate/up", True, 2, 1, 2, 16),
+                                                ("asym one weight", True, 2, 1, 1, 16)):
+            ahead += [(label, spec(4, 1, "f32", asym, ksn, spw, 1, -1, nwt, nsc)),
+                      (label + " ahead", spec(4, 1, "f32", asym, ksn, spw, 1, -1, nwt, nsc, True))]
+    return {"headline": head, "all": head + rest, "ahead": ahead}
 
 
 def find_tool(name):
@@ -267,7 +276,8 @@ def report(source, kernels, arch="gfx950", keep=None, with_code=False):
                 s = squash(sym)
                 if not s.startswith("void" + name + "<") and not s.startswith(name + "<"):
                     return False
-                return re.findall(r"-?\d+|true|false", s.split("<", 1)[1].split(">(")[0]) == args
+                got = re.findall(r"-?\d+|true|false", s.split("<", 1)[1].split(">(")[0])
+                return got == args or got == args + ["false"]  # a trailing template parameter left at its default
 
             sym = [s for s in funcs if same(s)]
             if len(sym) != 1:
@@ -296,7 +306,7 @@ COLS = ["preload", "pro_ins", "pro_B", "lgkm", "vm", "tail_B", "barriers", "tota
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--source", default=os.path.join(ROOT, "neural_amd", "csrc", "woq_gemv.hip"))
-    ap.add_argument("--set", default="all", choices=["all", "headline"])
+    ap.add_argument("--set", default="all", choices=["all", "headline", "ahead"])
     ap.add_argument("--legacy", action="store_true", help="the source has no woq_gemv_m1s_kernel: list the generic ones")
     ap.add_argument("--keep", default=None, help="directory to keep the wrapper source and the object in")
     ap.add_argument("--against", default=None, metavar="OTHER/woq_gemv.hip",

@@ -3,7 +3,11 @@
 For each Llama-2-7B decode shape, rotates enough distinct weight copies to defeat the 256 MB Infinity Cache, captures
 `reps` launches in one HIP graph and reports device time per launch (HIP events on the launch stream) and GB/s of
 algorithmic bytes, for every configuration given as NAME=VAL[,NAME=VAL...] env settings (NAD_GEMV_*).  With --trace
-(phase-trace library, `make -C neural_amd trace`) it also prints per-workgroup phase spans of the last launch.
+(phase-trace library, `make -C neural_amd trace`) it also prints per-workgroup phase spans of the last launch, and the
+stream rate the main loop's median implies.  Both orders of the M = 1 stream are read with
+`--trace base NAD_GEMV_AHEAD=0`: the first is the default (load-ahead where a form exists), the second the one-stage
+loop.  "stage arith" starts at an explicit vmcnt(0) in the one-stage loop; in the load-ahead order that wait stands in
+front of the next stage's loads, so the stamp starts behind it and includes their issue (the tool marks those rows).
 
 Usage: python tools/gemv_sweep.py [--trace] [--shapes qkv,o,...] CONFIG [CONFIG ...]
        CONFIG e.g. "base"  or  "NAD_GEMV_WAVES=8,NAD_GEMV_WPC=2"
@@ -127,12 +131,19 @@ def main():
                 print(f"    wg start offset   {q(s0 - t0)}")
                 print(f"    A + stage0 issued {q(s4 - s0)}")
                 print(f"    A staged (->bar)  {q(s1 - s0)}")
-                print(f"    main loop         {q(s2 - s1)}")
+                p50 = float(np.percentile((s2 - s1) * tick_us, 50))
+                print(f"    main loop         {q(s2 - s1)}  ({per / p50 / 1e6:.2f} TB/s at p50)")
                 print(f"    reduce+epilogue   {q(s3 - s2)}")
                 print(f"    wg end offset     {q(s3 - t0)}")
                 # the M = 1 kernels: wave 0's arithmetic per stage, each stage timed from an explicit wait for its
                 # loads -- the first one (its code is executed for the first time) against the later ones
                 first, later, nst = (buf[i, :grid].astype(np.int64) for i in (5, 6, 7))
+                if name == "gate_up":
+                    pl = bestla.plan_gate_up(ws[0][0], ws[0][1], 1)
+                else:
+                    pl = bestla.plan_qkv(*ws[0], 1) if name == "qkv" else ws[0][0].plan(1)
+                if pl["ahead"]:
+                    print("    load-ahead order: stage arith includes the issue of the next stage's loads")
                 if (nst > 0).any():
                     print(f"    first stage arith {q(first[nst > 0])}")
                 if (nst > 1).any():

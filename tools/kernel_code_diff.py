@@ -11,7 +11,8 @@ symbol with a kernel descriptor `<symbol>.kd` -- is compared by
   * its descriptor: the 64 descriptor bytes less the entry offset, and the metadata's VGPR / AGPR / SGPR counts,
     scratch (private segment), static LDS (group segment) and kernarg size.
 
-Nothing here looks for particular instructions.  Output: one line per object (kernels in a / in b / identical), then
+A kernel of b whose own template-id is one of a's plus a trailing `false` (a template parameter added at its default)
+is compared with that kernel of a.  Nothing here looks for particular instructions.  Output: one line per object (kernels in a / in b / identical), then
 every kernel that differs or exists on one side only, with its instruction and byte counts and registers on both
 sides.  Exit status 1 if any kernel present on both sides differs.
 """
@@ -98,6 +99,22 @@ def demangle(names):
     return dict(zip(names, out))
 
 
+def drop_trailing_false(name):
+    """`ret kernel<..., false>(params)` -> `ret kernel<...>(params)`: only the last argument of the kernel's own
+    template-id, found by matching brackets from the start of the name (nested template arguments and the parameter
+    list are left alone); anything else is returned unchanged"""
+    lt = name.find("<")
+    depth = 0
+    for i in range(lt, len(name)) if lt >= 0 else ():
+        depth += name[i] == "<"
+        depth -= name[i] == ">"
+        if depth == 0:
+            if name[i + 1:i + 2] == "(" and name[:i].endswith(", false"):
+                return name[:i - len(", false")] + name[i:]
+            break
+    return name
+
+
 def figures(co, sym, k):
     return "%6d ins %7d B  vgpr %3d agpr %3d sgpr %3d scratch %d lds %d kernarg %d" % (
         instructions(co, sym), len(k["code"]), k["vgpr_count"], k["agpr_count"], k["sgpr_count"],
@@ -123,6 +140,13 @@ def main():
             if ca is None or cb is None:
                 continue  # a host-only object
             ka, kb = kernels(ca), kernels(cb)
+            # a kernel template that gained a trailing parameter in b, left at `false`, is compared under its name in a
+            dem = demangle([n for n in ka if n not in kb] + [n for n in kb if n not in ka])
+            earlier = {dem[n]: n for n in ka if n not in kb}
+            for n in [n for n in kb if n not in ka]:
+                old = earlier.get(drop_trailing_false(dem[n]))
+                if old is not None:
+                    kb[old] = kb.pop(n)
             both = [n for n in ka if n in kb]
             diff = [n for n in both if ka[n] != kb[n]]
             only_a, only_b = [n for n in ka if n not in kb], [n for n in kb if n not in ka]
