@@ -201,8 +201,11 @@ int nad_device_forward(const void* act, int act_dtype, const void* devstor, floa
  * workspace sizing -- with every launch recorded instead of issued; no device memory is touched and no GPU is needed.
  * out (versioned by nout): [kernel NAD_KERNEL_*, grid, threads per workgroup, split-K runs, flags (bit 0: scale folded
  * into the fp16 weights; bit 1: gemm4 waves split over K; bit 2: the M = 1 decode launch takes the specialised
- * woq_gemv_m1s_kernel, see NAD_GEMV_M1_SPEC; bit 3: ... in its load-ahead order, see NAD_GEMV_AHEAD), launches
- * including pre-passes].  Returns the number of values written or -1. */
+ * woq_gemv_m1s_kernel, see NAD_GEMV_M1_SPEC; bit 3: ... in its load-ahead order, see NAD_GEMV_AHEAD; from bit 4, where
+ * the last main launch is a decode GEMV, the kernel instantiation its launch statement selected, 25 bits from the
+ * lowest: family 2 (1 woq_gemv_kernel, 2 woq_gemv_m1_kernel, 3 woq_gemv_m1s_kernel), log2 BITS 2, log2 GPT 2, ASYM 1,
+ * AT -- HILO for woq_gemv_kernel -- 2, KSN 3, SPW 3, NST 2, ST + 1 2, BATCH 1, NWT 2, NSC 2 (0, 7, 11, 16), AHEAD 1),
+ * launches including pre-passes].  Returns the number of values written or -1. */
 #define NAD_KERNEL_GEMV_M1 1   /* woq_gemv_m1_kernel: M = 1 decode */
 #define NAD_KERNEL_GEMV 2      /* woq_gemv_kernel: the stripe-stream GEMV, M <= 16 */
 #define NAD_KERNEL_SKINNY 3    /* woq_skinny_kernel: decode geometries the stream does not take */
@@ -426,6 +429,8 @@ void* nad_batch_create(const nad_batch_problem* problems, int n);
 int nad_batch_run(void* batch, void* queue);
 /* dry run of nad_batch_run: out as nad_plan_forward's (nothing is launched) */
 int nad_plan_batch(void* batch, int64_t* out, int nout);
+/* the same dry run for n problems on one weight, loaded or geometry-only (nad_weight_plan_only): no GPU needed */
+int nad_plan_batch_only(const void* devstor, int n, int64_t* out, int nout);
 void nad_batch_destroy(void* batch);
 
 /* ===== routed expert matmuls: ne_mul_mat_id / ne_mul_id_ffn_silu (neural_speed/core/ne_layers.c:2384-2462, 7783-7916,

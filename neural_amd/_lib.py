@@ -111,6 +111,7 @@ SIGNATURES = {
     "nad_batch_create": (_p, [_p, _i]),
     "nad_batch_run": (_i, [_p, _p]),
     "nad_plan_batch": (_i, [_p, _p, _i]),
+    "nad_plan_batch_only": (_i, [_p, _i, _p, _i]),
     "nad_batch_destroy": (None, [_p]),
     "nad_expert_bank_create": (_p, [_p, _i]),
     "nad_expert_bank_plan_only": (_p, [_p, _i]),

@@ -197,10 +197,26 @@ def plan_forward(bits, n, k, group_size=128, scale_dtype="fp16", asym=False, m=1
     return _plan_dict(o)
 
 
+def _gemv_instance(v):
+    """The decode GEMV instantiation a dry run's launch statement named (woq_kernels.h: gemv_inst), written as the
+    kernel's demangled template-id; None where the call's last main launch was no GEMV."""
+    f = lambda at, bits: (v >> at) & ((1 << bits) - 1)
+    b = lambda at: "true" if (v >> at) & 1 else "false"
+    family, bits, gpt, at = f(0, 2), 1 << f(2, 2), 1 << f(4, 2), f(7, 2)
+    ksn, spw, nst, st, nwt, nsc = f(9, 3), f(12, 3), f(15, 2), f(17, 2) - 1, f(20, 2), (0, 7, 11, 16)[f(22, 2)]
+    if family == 1:
+        return f"woq_gemv_kernel<{bits}, {at}, {gpt}, {b(6)}, {nst}>"
+    if family == 2:
+        return f"woq_gemv_m1_kernel<{bits}, {gpt}, {at}, {b(6)}, {ksn}, {spw}, {b(19)}, {nst}, {st}>"
+    if family == 3:
+        return f"woq_gemv_m1s_kernel<{bits}, {gpt}, {at}, {b(6)}, {ksn}, {spw}, {nst}, {st}, {nwt}, {nsc}, {b(24)}>"
+    return None
+
+
 def _plan_dict(o):
     return dict(kernel=KERNELS.get(int(o[0]), str(int(o[0]))), grid=int(o[1]), threads=int(o[2]), ksplit=int(o[3]),
                 fold=bool(o[4] & 1), ksw=bool(o[4] & 2), m1_spec=bool(o[4] & 4), ahead=bool(o[4] & 8),
-                launches=int(o[5]))
+                instance=_gemv_instance(int(o[4]) >> 4), launches=int(o[5]))
 
 
 def plan_qkv_forward(bits, nq, nk, nv, k, group_size=128, scale_dtype="fp16", asym=False, m=1, act="fp32"):
@@ -637,6 +653,15 @@ class Batch:
         o = np.zeros(6, np.int64)
         if lib().nad_plan_batch(self.handle, _ptr(o), 6) != 6:
             raise RuntimeError(f"nad_plan_batch failed: {last_error()}")
+        return _plan_dict(o)
+
+    @staticmethod
+    def plan_only(desc, n):
+        """what a batch of n problems on this weight launches; desc: plan_only_weight's descriptor or a DeviceWeight
+        (nad_plan_batch_only -- no GPU needed)"""
+        o = np.zeros(6, np.int64)
+        if lib().nad_plan_batch_only(getattr(desc, "desc", desc), n, _ptr(o), 6) != 6:
+            raise RuntimeError(f"nad_plan_batch_only failed: {last_error()}")
         return _plan_dict(o)
 
     def __del__(self):

@@ -97,6 +97,9 @@ bool planned(int kernel, int grid, int block, int ksplit, int fold, bool main) {
   }
   return true;
 }
+void plan_gemv_instance(uint32_t inst) {
+  if (t_plan) t_plan->fold |= int(inst) << nad::kPlanGemvInstShift;
+}
 
 // ------------------------------------------------------------------------------------------------ device context
 extern "C" void* bestla_create_device(bool profile) {

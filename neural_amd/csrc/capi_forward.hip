@@ -193,7 +193,7 @@ static int try_gemv(const Act& x, const Weights& W, const Epi& e, hipStream_t st
   const size_t lds = gemv_lds_layout(a, bits, waves, grid);
   const bool dry = planned(gemv_uses_m1(a, bits, waves) ? NAD_KERNEL_GEMV_M1 : NAD_KERNEL_GEMV, grid, waves * 64, 1,
                            !planning() ? 0 : (gemv_uses_m1s(a, bits, waves) ? 4 : 0) | (gemv_uses_ahead(a, bits, waves) ? 8 : 0));
-  return launch(dry, "gemv kernel", [&] { return launch_gemv(a, bits, waves, grid, lds, st); }) ? 1 : -1;
+  return launch_gemv_named(dry, "gemv kernel", [&] { return launch_gemv(a, bits, waves, grid, lds, st); }) ? 1 : -1;
 }
 
 static int run_i8(const Act& x, const Weights& W, bool dual, const Epi& e, hipStream_t st);
@@ -1291,6 +1291,10 @@ extern "C" void* nad_batch_create(const nad_batch_problem* p, int n) {
     const DeviceWeight* w = as_weight(p[i].weight);
     host[i] = GemvBatchEnt{p[i].act, w->tiles, w->scales, w->zps, p[i].out, {nullptr, nullptr, nullptr}};
   }
+  if (planning()) {  // nad_plan_batch_only: geometry-only weights, no table; nad_batch_run only records
+    b->a.batch = reinterpret_cast<const GemvBatchEnt*>(uintptr_t(1) << 44);
+    return b;
+  }
   if (hipMalloc(&b->dev, sizeof(GemvBatchEnt) * size_t(n)) != hipSuccess ||
       hipMemcpy(b->dev, host.data(), sizeof(GemvBatchEnt) * size_t(n), hipMemcpyHostToDevice) != hipSuccess) {
     set_err("nad_batch_create: device table allocation failed");
@@ -1305,14 +1309,15 @@ extern "C" void* nad_batch_create(const nad_batch_problem* p, int n) {
 extern "C" int nad_batch_run(void* batch, void* queue) {
   NadBatch* b = static_cast<NadBatch*>(batch);
   if (!b) return -1;
-  return launch(planned(NAD_KERNEL_GEMV_M1, b->grid, b->waves * 64), "nad_batch_run:", [&] {
+  return launch_gemv_named(planned(NAD_KERNEL_GEMV_M1, b->grid, b->waves * 64), "nad_batch_run:", [&] {
            return launch_gemv_batch(b->a, b->bits, b->waves, b->grid, b->lds, static_cast<hipStream_t>(queue));
          })
              ? 0
              : -1;
 }
 
-// Dry run of nad_batch_run: the record of nad_plan_forward (the batched launch has no specialised or load-ahead form).
+// Dry run of nad_batch_run: the record of nad_plan_forward (the batched launch has no specialised or load-ahead form),
+// the instantiation named by launch_gemv_batch's own launch statement.
 extern "C" int nad_plan_batch(void* batch, int64_t* out, int nout) {
   if (!batch || !out || nout < 0) {
     set_err("nad_plan_batch: bad arguments");
@@ -1322,6 +1327,32 @@ extern "C" int nad_plan_batch(void* batch, int64_t* out, int nout) {
   set_plan(&plan);
   const int rc = nad_batch_run(batch, nullptr);
   set_plan(nullptr);
+  if (rc) return -1;
+  const int64_t v[6] = {plan.kernel, plan.grid, plan.block, plan.ksplit, plan.fold, plan.launches};
+  const int c = nout < 6 ? nout : 6;
+  std::memcpy(out, v, sizeof(int64_t) * size_t(c));
+  return c;
+}
+
+// The same dry run for n problems on a loaded or geometry-only (nad_weight_plan_only) weight, no GPU needed: the batch
+// is created without its device table, recorded and destroyed.
+extern "C" int nad_plan_batch_only(const void* devstor, int n, int64_t* out, int nout) {
+  if (!devstor || n <= 0 || !out || nout < 0) {
+    set_err("nad_plan_batch_only: bad arguments");
+    return -1;
+  }
+  std::vector<nad_batch_problem> p(static_cast<size_t>(n));
+  for (auto& q : p) {
+    q.weight = devstor;
+    q.act = reinterpret_cast<const float*>(uintptr_t(1) << 42);  // aligned, never dereferenced on the host
+    q.out = reinterpret_cast<float*>(uintptr_t(1) << 43);
+  }
+  NadPlan plan;
+  set_plan(&plan);
+  void* b = nad_batch_create(p.data(), n);
+  const int rc = b ? nad_batch_run(b, nullptr) : -1;
+  set_plan(nullptr);
+  nad_batch_destroy(b);
   if (rc) return -1;
   const int64_t v[6] = {plan.kernel, plan.grid, plan.block, plan.ksplit, plan.fold, plan.launches};
   const int c = nout < 6 ? nout : 6;

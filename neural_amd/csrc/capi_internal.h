@@ -62,6 +62,17 @@ static inline bool launch(bool recorded, const char* what, F&& fn) {
   return false;
 }
 
+// The launch of a decode GEMV (launch_gemv, launch_gemv_batch).  In a dry run fn runs too, and the launch statement it
+// reaches names its kernel instead of launching (woq_kernels.h: gemv_name_begin); the name joins the record's flag word.
+void plan_gemv_instance(uint32_t inst);
+template <class F>
+static inline bool launch_gemv_named(bool recorded, const char* what, F&& fn) {
+  if (recorded) nad::gemv_name_begin();
+  const bool ok = launch(false, what, fn);
+  if (recorded) plan_gemv_instance(nad::gemv_name_end());
+  return ok;
+}
+
 // ------------------------------------------------------------------------------------------------ device context
 struct NadDevice {
   int device;

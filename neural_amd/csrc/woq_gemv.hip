@@ -1187,21 +1187,33 @@ static auto by_asym(const GemvArgs& a, F f) {
   return a.asym ? f(std::true_type{}) : f(std::false_type{});
 }
 
+// Every launch of the three forward kernels goes through here with its template arguments packed (gemv_inst): in a dry
+// run the statement that would have launched names its kernel instead (gemv_named).
+template <auto K, class... Args>
+static hipError_t gemv_issue(uint32_t inst, dim3 g, dim3 b, size_t lds, hipStream_t st, const Args&... args) {
+  return gemv_named(inst) ? hipSuccess : launch_big_lds<K>(g, b, lds, st, args...);
+}
+
 template <int BITS, int HILO, int GPT, bool ASYM>
 static hipError_t gemv_launch4(const GemvArgs& a, dim3 g, dim3 b, size_t lds, hipStream_t st) {
   const int spw = m1_stages_per_wave(a, KS, int(b.x / 64));
   const int nst = a.m1_nst == 1 ? 1 : (a.m1_nst == 3 ? 3 : (spw <= 2 ? 1 : 3));
-  return nst == 1 ? launch_big_lds<woq_gemv_kernel<BITS, HILO, GPT, ASYM, 1>>(g, b, lds, st, a)
-                  : launch_big_lds<woq_gemv_kernel<BITS, HILO, GPT, ASYM, 3>>(g, b, lds, st, a);
+  constexpr auto inst = [](int n) { return gemv_inst(1, BITS, GPT, ASYM, HILO, 0, 0, n, -1, false, 0, 0, false); };
+  return nst == 1 ? gemv_issue<woq_gemv_kernel<BITS, HILO, GPT, ASYM, 1>>(inst(1), g, b, lds, st, a)
+                  : gemv_issue<woq_gemv_kernel<BITS, HILO, GPT, ASYM, 3>>(inst(3), g, b, lds, st, a);
 }
 
 template <int BITS, int GPT, int AT, bool ASYM, int KSN, int SPW, int ST>
 static hipError_t gemv_m1_launch5(const GemvArgs& a, dim3 g, dim3 b, size_t lds, hipStream_t st) {
+  constexpr auto inst = [](bool batch, int n) {
+    return gemv_inst(2, BITS, GPT, ASYM, AT, KSN, SPW, n, ST, batch, 0, 0, false);
+  };
   if (a.batch)
-    return launch_big_lds<woq_gemv_m1_kernel<BITS, GPT, AT, ASYM, KSN, SPW, true, NAD_M1_BATCH_NST, ST>>(g, b, lds, st, a);
+    return gemv_issue<woq_gemv_m1_kernel<BITS, GPT, AT, ASYM, KSN, SPW, true, NAD_M1_BATCH_NST, ST>>(
+        inst(true, NAD_M1_BATCH_NST), g, b, lds, st, a);
   return m1_nst(a, KSN, int(b.x / 64)) == 1
-             ? launch_big_lds<woq_gemv_m1_kernel<BITS, GPT, AT, ASYM, KSN, SPW, false, 1, ST>>(g, b, lds, st, a)
-             : launch_big_lds<woq_gemv_m1_kernel<BITS, GPT, AT, ASYM, KSN, SPW, false, 2, ST>>(g, b, lds, st, a);
+             ? gemv_issue<woq_gemv_m1_kernel<BITS, GPT, AT, ASYM, KSN, SPW, false, 1, ST>>(inst(false, 1), g, b, lds, st, a)
+             : gemv_issue<woq_gemv_m1_kernel<BITS, GPT, AT, ASYM, KSN, SPW, false, 2, ST>>(inst(false, 2), g, b, lds, st, a);
 }
 // int2: the scale type as a template parameter (3 x the int2 instantiations; int4 keeps the runtime form)
 #ifndef NAD_INT2_ST
@@ -1257,9 +1269,10 @@ static hipError_t m1s_go(const GemvArgs& a, dim3 g, dim3 b, size_t lds, hipStrea
   const uint32_t uqr = uint32_t(a.u_q) | uint32_t(a.u_r) << 16;
   const uint32_t geom = uint32_t(a.nt) | uint32_t(a.ng) << kM1GeomNgShift | uint32_t(a.tpg_shift) << kM1GeomTpgShift |
                         uint32_t(a.scale_t) << kM1GeomScaleShift | uint32_t(b.x / 64) << kM1GeomWavesShift;
-  return launch_big_lds<woq_gemv_m1s_kernel<BITS, GPT, AT, ASYM, KSN, SPW, NST, ST, NWT, NSC, AHEAD>>(
-      g, b, lds, st, a.A, a.w[0].tiles, a.w[0].scales, NWT > 1 ? a.w[1].tiles : nullptr,
-      NWT > 1 ? a.w[1].scales : nullptr, a.K * esz, uqr, geom, a.w[0].ns, m1s_rest<NWT>(a));
+  return gemv_issue<woq_gemv_m1s_kernel<BITS, GPT, AT, ASYM, KSN, SPW, NST, ST, NWT, NSC, AHEAD>>(
+      gemv_inst(3, BITS, GPT, ASYM, AT, KSN, SPW, NST, ST, false, NWT, NSC, AHEAD), g, b, lds, st, a.A, a.w[0].tiles,
+      a.w[0].scales, NWT > 1 ? a.w[1].tiles : nullptr, NWT > 1 ? a.w[1].scales : nullptr, a.K * esz, uqr, geom,
+      a.w[0].ns, m1s_rest<NWT>(a));
 }
 // weights of the launch as woq_gemv_m1s_kernel's NWT (0: not served)
 static int m1s_nwt(const GemvArgs& a, int waves) {
@@ -1409,6 +1422,21 @@ hipError_t gemv_m1_launch_b2(const GemvArgs& a, int gpt, dim3 g, dim3 b, size_t 
 hipError_t gemv_m1_launch_b2(const GemvArgs& a, int gpt, dim3 g, dim3 b, size_t lds, hipStream_t st);
 #endif
 #if !defined(GEMV_PART) || GEMV_PART == 0
+static thread_local uint32_t t_named = 0;
+static thread_local bool t_naming = false;
+void gemv_name_begin() {
+  t_naming = true;
+  t_named = 0;
+}
+uint32_t gemv_name_end() {
+  t_naming = false;
+  return t_named;
+}
+bool gemv_named(uint32_t inst) {
+  if (t_naming) t_named = inst;
+  return t_naming;
+}
+
 static hipError_t gemv_m1_launch(const GemvArgs& a, int bits, int gpt, dim3 g, dim3 b, size_t lds, hipStream_t st) {
   if (bits == 4) {
     if (gpt == 1) return gemv_m1_launch2<4, 1>(a, g, b, lds, st);

@@ -425,6 +425,24 @@ int gemv_waves(int bits, int nt, int ng, int bs);
 // 4 = never)
 void gemv_lean_slices(GemvArgs& a, int bits, int* waves, int ks_pref);
 hipError_t launch_gemv(const GemvArgs& a, int bits, int waves, int grid, size_t lds, hipStream_t stream);
+// Dry runs (nad_plan_*): between gemv_name_begin() and gemv_name_end() on the calling thread launch_gemv and
+// launch_gemv_batch run as always up to the launch itself, which records its kernel's template arguments instead of
+// being issued -- the name comes from the statement that would have launched.  gemv_name_end() returns the record of the
+// last such launch (gemv_inst below), 0 if there was none.
+void gemv_name_begin();
+uint32_t gemv_name_end();
+bool gemv_named(uint32_t inst);  // woq_gemv.hip's launch statements: true (and inst recorded) while naming
+// family 1 woq_gemv_kernel (at = HILO; ksn, spw, st, nwt, nsc: 0 / -1), 2 woq_gemv_m1_kernel, 3 woq_gemv_m1s_kernel;
+// bits, gpt in {1, 2, 4, 8}; st -1..2; nsc in {0, 7, 11, 16}
+constexpr uint32_t gemv_inst(int family, int bits, int gpt, bool asym, int at, int ksn, int spw, int nst, int st,
+                             bool batch, int nwt, int nsc, bool ahead) {
+  const auto lg = [](int v) { return uint32_t(v >= 8 ? 3 : (v >= 4 ? 2 : (v >= 2 ? 1 : 0))); };
+  return uint32_t(family) | lg(bits) << 2 | lg(gpt) << 4 | uint32_t(asym) << 6 | uint32_t(at) << 7 |
+         uint32_t(ksn) << 9 | uint32_t(spw) << 12 | uint32_t(nst) << 15 | uint32_t(st + 1) << 17 |
+         uint32_t(batch) << 19 | uint32_t(nwt) << 20 | uint32_t(nsc == 16 ? 3 : (nsc == 11 ? 2 : nsc == 7)) << 22 |
+         uint32_t(ahead) << 24;
+}
+constexpr int kPlanGemvInstShift = 4;  // the record's place in the plan's flag word (o[4] of nad_plan_*)
 // whether launch_gemv would take woq_gemv_m1_kernel for these arguments
 bool gemv_uses_m1(const GemvArgs& a, int bits, int waves);
 // ... and would serve it with woq_gemv_m1s_kernel (a.m1_spec, and an instantiation for the launch exists)

@@ -109,6 +109,10 @@ def test_launcher_choice(knob):
         p = plan()
         assert p["kernel"] == "woq_gemv_m1_kernel" and p["m1_spec"] is True and p["ahead"] is True, (name, p)
     assert LLAMA["qkv"]()["threads"] == 1024 and LLAMA["gate_up"]()["threads"] == 1024
+    # ... by name: 16 waves of one 2-tile slice, one register stage, 3 weights / the pair, 16 slots, load-ahead
+    assert LLAMA["qkv"]()["instance"] == "woq_gemv_m1s_kernel<4, 1, 0, false, 2, 1, 1, -1, 3, 16, true>"
+    assert LLAMA["gate_up"]()["instance"] == "woq_gemv_m1s_kernel<4, 1, 0, false, 2, 1, 1, -1, 2, 16, true>"
+    assert NEVER["dual_qkv"]()["instance"] is None  # woq_gemv_m1_dual_kernel: not one of the three named families
     p = bestla.plan_qkv_forward(4, 4096, 4096, 4096, 4096, scale_dtype="bf16", asym=True)
     assert p["ahead"] is True, p
     for name, plan in list(NEVER.items()):
