@@ -396,6 +396,8 @@ int nad_device_get_rows(const void* devstor, const int32_t* ids, int ids_stride,
  * nad_plan_weight's -- [NAD_KERNEL_GET_ROWS, grid, threads per workgroup, 1, 0, launches]; a unit of work is (row, 16 K
  * tiles) -- Q6_K: (row, 4 superblocks) -- and a workgroup takes four.  Returns the number of values written or -1. */
 #define NAD_KERNEL_GET_ROWS 20 /* woq_get_rows_kernel / woq_get_rows_q6k_kernel: ne_get_rows on a device weight */
+#define NAD_KERNEL_GEMV_ROUTED_GENERAL 21 /* woq_gemv_routed_kernel: routed expert matmuls of a general bank's int4 g32 /
+                                             int8 weights on the stripe stream (nad_plan_moe) */
 int nad_plan_get_rows(const void* devstor, int m, int out_dtype, int64_t* out, int nout);
 /* A geometry-only weight descriptor for the dry runs, no GPU needed: bits 2 / 4 / 8 (blocksize <= 0 = per-channel,
  * scale_t NAD_SCALE_*, act_order != 0: a desc_act weight) or 6 (Q6_K, k % 256 == 0; the other arguments are ignored).
@@ -448,8 +450,23 @@ void* nad_expert_bank_create(const void* const* weights, int n_expert);
  * [bits (2, 4, 8; 6 = GGUF Q6_K), n, k, blocksize (<= 0: per-channel), NAD_SCALE_*, asym].  It holds no weights: the
  * launching entries below refuse it (-1). */
 void* nad_expert_bank_plan_only(const int32_t* geom, int n_expert);
+/* The same two entries with flags.  flags = 0: exactly the entries above ("a bank that exists runs on the M = 1
+ * stream").  NAD_BANK_GENERAL: the bank also takes the weights that the stripe-stream GEMV (woq_gemv_kernel, hi / lo
+ * fp16 rows) runs at M = 1 with fp32 rows and the M = 1 stream does not:
+ *   int4 groups of 32, symmetric (the reference's default quantization; GGUF Q4_0)
+ *   int8 groups of 32 or 64 * 2^j, per-channel included, symmetric or asymmetric (S8, S5..S7; GGUF Q8_0, Q5_0)
+ * with any scale type.  Such a bank is served by woq_gemv_routed_kernel (route kind 1) under the same contract: every
+ * routed row bit-identical to the expert's own M = 1 forward, ids read on the device, one launch per matmul.  A bank
+ * whose format the M = 1 stream takes is the bank the entries above make (route kind 0), whichever entry made it.
+ * Still refused, by name: block mins (Q4_1 / Q5_1), Q6_K, NFloat codes, act-order, integer-compute weights, and int4
+ * groups of 32 with zero points (the skinny kernel's).  The gate / up pair and the down bank of one FFN may be of
+ * different kinds (Q4_0 gate / up with an int4 g128 down). */
+#define NAD_BANK_GENERAL 1u
+void* nad_expert_bank_create_ex(const void* const* weights, int n_expert, unsigned flags);
+void* nad_expert_bank_plan_only_ex(const int32_t* geom, int n_expert, unsigned flags);
 void nad_expert_bank_destroy(void* bank);
-/* [n_expert, bits, n, k, blocksize, scale_t, asym, holds weights]; writes min(nout, 8) values, returns the count or -1 */
+/* [n_expert, bits, n, k, blocksize, scale_t, asym, holds weights, route kind (0 the M = 1 stream, 1 the stripe stream)];
+ * writes min(nout, 9) values, returns the count or -1 */
 int nad_expert_bank_info(const void* bank, int64_t* out, int nout);
 /* ne_mul_mat_id: out[r][0:n] = act[r][0:k] . W[ids[r * ids_ld + slot]]^T for r < m, ONE launch
  * (woq_gemv_m1_routed_kernel: workgroups dealt out row by row, each row exactly the arithmetic of its expert's own M = 1
@@ -492,8 +509,8 @@ int nad_device_moe_ffn(const void* gate_bank, const void* up_bank, const void* d
 int nad_moe_route(const float* logits, int ld, int m, int n_expert, int top_k, int32_t* ids, int ids_ld, float* wts,
                   int wts_ld, void* queue);
 /* Dry run of nad_device_moe_ffn (no launch, no GPU needed; geometry-only banks qualify): per launch [kernel
- * NAD_KERNEL_*, grid, threads per workgroup, dynamic LDS bytes] -- 1 gate + up, 2 down (both NAD_KERNEL_GEMV_ROUTED,
- * grid = m * top_k * workgroups per problem), 3 combine -- then the launch count: 13 values.  Writes min(nout, 13),
+ * NAD_KERNEL_*, grid, threads per workgroup, dynamic LDS bytes] -- 1 gate + up, 2 down (each NAD_KERNEL_GEMV_ROUTED, or
+ * NAD_KERNEL_GEMV_ROUTED_GENERAL for a bank of route kind 1; grid = m * top_k * workgroups per problem), 3 combine -- then the launch count: 13 values.  Writes min(nout, 13),
  * returns the number written or -1. */
 int nad_plan_moe(const void* gate_bank, const void* up_bank, const void* down_bank, int m, int top_k, int64_t* out,
                  int nout);
@@ -505,9 +522,10 @@ int nad_plan_moe(const void* gate_bank, const void* up_bank, const void* down_ba
  * follows the ids it finds.  The sort is a function of ids alone (a stable counting sort, no atomics).
  *
  * A bank is taken when every expert's format is one gemm7 has (recorded at bank creation): int4 groups of 64 or
- * 128 * 2^j, int2 groups of 64 * 2^j (groups of 32 have no bank: nad_expert_bank_create refuses them), sym or asym, any
+ * 128 * 2^j, int2 groups of 64 * 2^j, and for a bank of route kind 1 (NAD_BANK_GENERAL) int4 groups of 32 and int8
+ * groups of 32 or 64 * 2^j, sym or asym, any
  * scale type, every q * s inside the fp16 range (geometry-only banks count as such).  The FFN also needs fmid to be a whole number of the down bank's K tiles (128
- * int4, 256 int2).  Anything else: -1 before any launch, nad_last_error() naming the bank and the reason -- never the
+ * int4, 256 int2, 64 int8).  Anything else: -1 before any launch, nad_last_error() naming the bank and the reason -- never the
  * row-routed path in its place.
  *
  * Arithmetic: the activations are rounded to fp16 and q * s is rounded once to fp16, as in every gemm7 forward; an

@@ -115,6 +115,8 @@ SIGNATURES = {
     "nad_batch_destroy": (None, [_p]),
     "nad_expert_bank_create": (_p, [_p, _i]),
     "nad_expert_bank_plan_only": (_p, [_p, _i]),
+    "nad_expert_bank_create_ex": (_p, [_p, _i, _u32]),
+    "nad_expert_bank_plan_only_ex": (_p, [_p, _i, _u32]),
     "nad_expert_bank_destroy": (None, [_p]),
     "nad_expert_bank_info": (_i, [_p, _p, _i]),
     "nad_device_mul_mat_id": (_i, [_p, _p, _p, _i, _i, _p, _i, _i, _i, _p]),

@@ -182,7 +182,7 @@ KERNELS = {1: "woq_gemv_m1_kernel", 2: "woq_gemv_kernel", 3: "woq_skinny_kernel"
            9: "woq_gemm7_kernel", 10: "woq_mid_kernel", 11: "woq_q6k_gemv_kernel", 12: "woq_q6k_gemm_kernel",
            13: "woq_q6k_i8_kernel", 14: "woq_gemv_m1_routed_kernel", 15: "moe_combine_kernel", 16: "moe_sort_kernel",
            17: "nad_cvt_act_kernel", 18: "woq_gemm7_grouped_kernel", 19: "moe_gather_kernel",
-           20: "woq_get_rows_kernel"}
+           20: "woq_get_rows_kernel", 21: "woq_gemv_routed_kernel"}
 
 
 def plan_forward(bits, n, k, group_size=128, scale_dtype="fp16", asym=False, m=1, act="fp32"):
@@ -676,35 +676,44 @@ class Batch:
 
 # ---------------------------------------------------------------------------------------------------- routed experts
 _SCALE_CODE = {"fp32": 0, "bf16": 1, "fp16": 2}
+BANK_GENERAL = 1  # NAD_BANK_GENERAL
 
 
 class ExpertBank:
     """The expert weights of one matmul of a Mixtral-style FFN layer (include/neural_amd.h nad_expert_bank_*): a list of
     DeviceWeights of one shape and format, held as one device table the routed kernel indexes with ids it reads on the
-    device.  The weights are kept alive with the bank."""
+    device.  The weights are kept alive with the bank.  general=True (NAD_BANK_GENERAL) also takes the weights the
+    stripe-stream GEMV runs at M = 1 and the M = 1 stream does not -- int4 groups of 32 sym, int8 (GGUF Q4_0, Q5_0,
+    Q8_0) -- served by woq_gemv_routed_kernel; route is 0 for the M = 1 stream, 1 for the stripe stream."""
 
-    def __init__(self, weights, _handle=None):
+    def __init__(self, weights, general=False, _handle=None):
         self._keep = list(weights)
         if _handle is None:
             arr = (C.c_void_p * len(self._keep))(*[C.cast(w.desc, C.c_void_p) for w in self._keep])
-            _handle = lib().nad_expert_bank_create(arr, len(self._keep))
+            if general:
+                _handle = lib().nad_expert_bank_create_ex(arr, len(self._keep), BANK_GENERAL)
+            else:
+                _handle = lib().nad_expert_bank_create(arr, len(self._keep))
             if not _handle:
-                raise RuntimeError(f"nad_expert_bank_create failed: {last_error()}")
+                raise RuntimeError(f"nad_expert_bank_create{'_ex' if general else ''} failed: {last_error()}")
         self.handle = _handle
-        o = np.zeros(8, np.int64)
-        if lib().nad_expert_bank_info(self.handle, _ptr(o), 8) != 8:
+        o = np.zeros(9, np.int64)
+        if lib().nad_expert_bank_info(self.handle, _ptr(o), 9) != 9:
             raise RuntimeError(f"nad_expert_bank_info failed: {last_error()}")
-        (self.n_expert, self.bits, self.n, self.k, self.blocksize, self.scale_t, self.asym, self.has_weights) = (
-            int(v) for v in o)
+        (self.n_expert, self.bits, self.n, self.k, self.blocksize, self.scale_t, self.asym, self.has_weights,
+         self.route) = (int(v) for v in o)
 
     @classmethod
-    def plan_only(cls, geometries):
+    def plan_only(cls, geometries, general=False):
         """A geometry-only bank for plan_moe (no GPU needed, the same checks as a real bank): geometries is a list of
         (bits, n, k, group_size, scale_dtype, asym) per expert; bits 6 names GGUF Q6_K."""
         g = np.array([[b, n, k, gs, _SCALE_CODE[st], int(asym)] for b, n, k, gs, st, asym in geometries], np.int32)
-        h = lib().nad_expert_bank_plan_only(_ptr(g), len(g))
+        if general:
+            h = lib().nad_expert_bank_plan_only_ex(_ptr(g), len(g), BANK_GENERAL)
+        else:
+            h = lib().nad_expert_bank_plan_only(_ptr(g), len(g))
         if not h:
-            raise RuntimeError(f"nad_expert_bank_plan_only failed: {last_error()}")
+            raise RuntimeError(f"nad_expert_bank_plan_only{'_ex' if general else ''} failed: {last_error()}")
         return cls([], _handle=h)
 
     def __del__(self):
@@ -838,7 +847,7 @@ def moe_grouped_workspace_rows(ws, gate, up, down, m, top_k):
     [np][fout], and for the FFN t16 / u16 fp16 [np][fmid])."""
     torch = _torch()
     np_, ne = m * top_k, gate.n_expert
-    ktile = 128 if gate.bits == 4 else 256
+    ktile = {4: 128, 2: 256, 8: 64}[gate.bits]
     kp = (gate.k + ktile - 1) // ktile * ktile
     fout = down.n if down is not None else gate.n
     o = [0]

@@ -171,7 +171,7 @@ static int prepare_gemv(GemvArgs& a, int& waves, int& grid, const Act& x, const 
 // One M = 1 fp32 problem on ws[0] (nw = 1), or on the {gate, up} pair ws[0], ws[1] with a dual epilogue (nw = 2), as
 // its own decode launch prepares it (capi_moe.hip: the routed launch runs every problem at exactly this geometry).  The
 // pointers in `a` are placeholders.
-bool prepare_m1_problem(GemvArgs& a, int& waves, const DeviceWeight* const* ws, int nw, int epi) {
+static bool prepare_one_problem(GemvArgs& a, int& waves, const DeviceWeight* const* ws, int nw, int epi) {
   const float* act = reinterpret_cast<const float*>(uintptr_t(1) << 42);  // aligned, never dereferenced on the host
   float* y = reinterpret_cast<float*>(uintptr_t(1) << 43);
   float* outs[2] = {y, y};
@@ -179,8 +179,14 @@ bool prepare_m1_problem(GemvArgs& a, int& waves, const DeviceWeight* const* ws, 
   Epi e;
   e.kind = epi;
   int grid = 0;
-  return prepare_gemv(a, waves, grid, Act{act, kActF32, ws[0]->k, 1, ws[0]->k}, Weights{nw, ws, outs, ldos}, e) &&
-         gemv_uses_m1(a, ws[0]->bits, waves);
+  return prepare_gemv(a, waves, grid, Act{act, kActF32, ws[0]->k, 1, ws[0]->k}, Weights{nw, ws, outs, ldos}, e);
+}
+bool prepare_m1_problem(GemvArgs& a, int& waves, const DeviceWeight* const* ws, int nw, int epi) {
+  return prepare_one_problem(a, waves, ws, nw, epi) && gemv_uses_m1(a, ws[0]->bits, waves);
+}
+// ... the same problem on the stripe-stream kernel: what try_gemv launches where gemv_uses_m1 is false
+bool prepare_general_problem(GemvArgs& a, int& waves, const DeviceWeight* const* ws, int nw, int epi) {
+  return prepare_one_problem(a, waves, ws, nw, epi) && !gemv_uses_m1(a, ws[0]->bits, waves);
 }
 
 // 1 launched, 0 not eligible, -1 launch error

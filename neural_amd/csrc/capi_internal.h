@@ -183,6 +183,9 @@ int ffn_forward(const void* act, int act_dtype, const void* w1p, const void* w2p
 // launch prepares them; false where the M = 1 GEMV does not take the geometry
 int device_cus();
 bool prepare_m1_problem(nad::GemvArgs& a, int& waves, const nad::DeviceWeight* const* ws, int nw, int epi);
+// ... the same problem where the stripe-stream GEMV (woq_gemv_kernel, hi / lo fp16 rows) serves it and the M = 1 stream
+// does not: false where prepare_gemv refuses the geometry or the M = 1 stream takes it
+bool prepare_general_problem(nad::GemvArgs& a, int& waves, const nad::DeviceWeight* const* ws, int nw, int epi);
 // ... and the tile height a gemm7 launch of m rows on w takes (NAD_GEMM7_BM, else the cost model), and w's K tile
 int gemm7_tile_height(const nad::DeviceWeight& w, int m);
 int gemm7_k_tile(const nad::DeviceWeight& w);

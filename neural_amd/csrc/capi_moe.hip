@@ -1,7 +1,8 @@
 // capi_moe.hip -- Mixtral-style expert FFNs with the routing read on the device (include/neural_amd.h, "routed expert
 // matmuls"): the expert bank, nad_device_mul_mat_id (ne_mul_mat_id, ne_layers.c:2384-2462, 7783-7916),
 // nad_device_moe_ffn (models/llama/llama.cpp:641-679), the router (llama.cpp:624-638) and the dry run.  The hot path is
-// woq_gemv_m1_routed_kernel (woq_gemv.hip); the bank's device table is the feature's only allocation.  For prefill
+// woq_gemv_m1_routed_kernel, or woq_gemv_routed_kernel for a general bank's int4 g32 / int8 weights (woq_gemv.hip); the
+// bank's device table is the feature's only allocation.  For prefill
 // sizes the sorted, grouped entries (nad_device_moe_ffn_grouped, nad_device_mul_mat_id_grouped): moe_sort_kernel
 // (woq_moe.hip), then woq_gemm7_grouped_kernel (woq_gemm7.hip) over every expert's sorted rows.
 #include <algorithm>
@@ -22,7 +23,9 @@ struct NadExpertBank {
   DeviceWeight w0{};             // the shape and format every expert shares (its pointers are expert 0's)
   GemvExpertEnt* dev = nullptr;  // [n_expert]; null for a geometry-only bank (nad_expert_bank_plan_only)
   bool g7_ok = false;            // every expert takes gemm7 (gemm7_ok, stripe-major): the grouped entries serve the bank
+  int kind = 0;                  // the routed launch that serves it: 0 the M = 1 stream, 1 the stripe stream (NAD_BANK_GENERAL)
 };
+constexpr int kBankLean = 0, kBankStripe = 1;
 
 const NadExpertBank* as_bank(const void* p, const char* who, const char* role) {
   const auto* b = static_cast<const NadExpertBank*>(p);
@@ -34,17 +37,20 @@ const NadExpertBank* as_bank(const void* p, const char* who, const char* role) {
 }
 
 // nad_batch_create's conditions, per expert (the callers have checked 1 <= n <= kMaxExperts)
-bool bank_check(const DeviceWeight* const* ws, int n, const char* who) {
+// general (NAD_BANK_GENERAL): also the weights the stripe-stream GEMV runs at M = 1 where the M = 1 stream does not --
+// int4 groups of 32 sym, int8 -- with kind set to the launch that serves the bank
+bool bank_check(const DeviceWeight* const* ws, int n, const char* who, bool general, int& kind) {
   const DeviceWeight& w0 = *ws[0];
+  kind = kBankLean;
   for (int i = 0; i < n; i++) {
     const DeviceWeight& w = *ws[i];
     if (is_q6k(w)) {  // the routed GEMV streams the int4 / int2 tile layouts only
       set_err("%s: expert %d's weight is GGUF Q6_K, which the routed GEMV does not stream", who, i);
       return false;
     }
-    if ((w.bits != 4 && w.bits != 2) || w.f4kind >= 0) {
-      set_err("%s: expert %d's weight is not in the int4 / int2 tile layout (bits %d%s)", who, i, w.bits,
-              w.f4kind >= 0 ? ", NFloat codes" : "");
+    if ((w.bits != 4 && w.bits != 2 && !(general && w.bits == 8)) || w.f4kind >= 0) {
+      set_err("%s: expert %d's weight is not in the int4 / int2%s tile layout (bits %d%s)", who, i,
+              general ? " / int8" : "", w.bits, w.f4kind >= 0 ? ", NFloat codes" : "");
       return false;
     }
     if (w.n != w0.n || w.k != w0.k || w.bits != w0.bits || w.blocksize != w0.blocksize || w.asym != w0.asym ||
@@ -67,19 +73,32 @@ bool bank_check(const DeviceWeight* const* ws, int n, const char* who) {
   }
   GemvArgs a{};
   int waves = 0;
-  if (!prepare_m1_problem(a, waves, ws, 1, kEpiNone)) {
+  if (prepare_m1_problem(a, waves, ws, 1, kEpiNone)) return true;
+  if (!general) {
     set_err("%s: expert 0's weight geometry (n %d, k %d, group %d) does not take the M = 1 GEMV", who, w0.n, w0.k,
             w0.blocksize);
     return false;
   }
+  if (w0.bits == 4 && w0.blocksize == 32 && w0.asym) {
+    set_err("%s: int4 groups of 32 with zero points run on the skinny kernel, which is not routed", who);
+    return false;
+  }
+  if (!((w0.bits == 4 && w0.blocksize == 32) || w0.bits == 8) || !prepare_general_problem(a, waves, ws, 1, kEpiNone)) {
+    set_err("%s: expert 0's weight geometry (int%d, n %d, k %d, group %d) takes neither the M = 1 GEMV nor the routed "
+            "stripe stream (int4 groups of 32 sym; int8 groups of 32, 64 * 2^j or one per channel)", who, w0.bits, w0.n,
+            w0.k, w0.blocksize);
+    return false;
+  }
+  kind = kBankStripe;
   return true;
 }
 
 // One routed launch: the GemvArgs of one problem, the workgroups per problem and the grid
 struct RoutedGeom {
   GemvArgs a{};
-  int bits = 0, waves = 0, wpp = 0, grid = 0;
+  int bits = 0, waves = 0, wpp = 0, grid = 0, kind = kBankLean;
   size_t lds = 0;
+  int kernel() const { return kind == kBankStripe ? NAD_KERNEL_GEMV_ROUTED_GENERAL : NAD_KERNEL_GEMV_ROUTED; }
 };
 
 // up == nullptr: one weight per problem; else the {gate, up} pair under the dual epilogue epi.  Workgroups per
@@ -88,8 +107,10 @@ struct RoutedGeom {
 bool routed_geometry(RoutedGeom& g, const NadExpertBank& w, const NadExpertBank* up, int epi, int64_t nprob,
                      const char* who) {
   const DeviceWeight* ws[2] = {&w.w0, up ? &up->w0 : nullptr};
-  if (!prepare_m1_problem(g.a, g.waves, ws, up ? 2 : 1, epi)) {
-    set_err("%s: this weight geometry does not take the M = 1 GEMV", who);
+  g.kind = w.kind;
+  if (!(g.kind == kBankStripe ? prepare_general_problem : prepare_m1_problem)(g.a, g.waves, ws, up ? 2 : 1, epi)) {
+    set_err("%s: this weight geometry does not take the %s", who,
+            g.kind == kBankStripe ? "routed stripe stream" : "M = 1 GEMV");
     return false;
   }
   g.bits = w.w0.bits;
@@ -116,8 +137,12 @@ bool routed_geometry(RoutedGeom& g, const NadExpertBank& w, const NadExpertBank*
 
 int run_routed(const RoutedGeom& g, GemvRouted r, hipStream_t st) {
   r.wpp = g.wpp;
-  return launch(planned(NAD_KERNEL_GEMV_ROUTED, g.grid, g.waves * 64), "routed gemv kernel",
-                [&] { return launch_gemv_routed(g.a, r, g.bits, g.waves, g.grid, g.lds, st); })
+  return launch(planned(g.kernel(), g.grid, g.waves * 64), "routed gemv kernel",
+                [&] {
+                  return g.kind == kBankStripe
+                             ? launch_gemv_routed_general(g.a, r, g.bits, g.waves, g.grid, g.lds, st)
+                             : launch_gemv_routed(g.a, r, g.bits, g.waves, g.grid, g.lds, st);
+                })
              ? 0
              : -1;
 }
@@ -161,21 +186,29 @@ bool pair_ok(const NadExpertBank& g, const NadExpertBank& u, const NadExpertBank
 
 size_t ws_part(int64_t rows, int cols) { return size_t(align256(uint64_t(rows) * uint64_t(cols) * sizeof(float))); }
 
-NadExpertBank* bank_new(const DeviceWeight* const* ws, int n, const char* who) {
-  if (!bank_check(ws, n, who)) return nullptr;
+NadExpertBank* bank_new(const DeviceWeight* const* ws, int n, const char* who, bool general) {
+  int kind = kBankLean;
+  if (!bank_check(ws, n, who, general, kind)) return nullptr;
   auto* b = new NadExpertBank();
   b->n_expert = n;
   b->w0 = *ws[0];
+  b->kind = kind;
   b->g7_ok = true;
+  // groups of 32 (a stripe-stream bank's) have grouped gemm7 instantiations too; a lean bank never holds them
   for (int i = 0; i < n; i++)
-    b->g7_ok = b->g7_ok && !ws[i]->kmajor && ws[i]->blocksize >= 64 &&
+    b->g7_ok = b->g7_ok && !ws[i]->kmajor && (kind == kBankStripe || ws[i]->blocksize >= 64) &&
                gemm7_ok(ws[i]->bits, ws[i]->blocksize, ws[i]->fold_ok);
   return b;
 }
-}  // namespace
 
-extern "C" void* nad_expert_bank_create(const void* const* weights, int n_expert) {
-  const char* who = "nad_expert_bank_create";
+bool flags_ok(unsigned flags, const char* who) {
+  if ((flags & ~NAD_BANK_GENERAL) == 0) return true;
+  set_err("%s: unknown flags 0x%x (NAD_BANK_GENERAL is the only one)", who, flags);
+  return false;
+}
+
+void* bank_create(const void* const* weights, int n_expert, unsigned flags, const char* who) {
+  if (!flags_ok(flags, who)) return nullptr;
   if (!weights || n_expert < 1 || n_expert > kMaxExperts) {
     set_err("%s: need 1..%d experts (got %d)", who, kMaxExperts, n_expert);
     return nullptr;
@@ -186,7 +219,7 @@ extern "C" void* nad_expert_bank_create(const void* const* weights, int n_expert
       set_err("%s: expert %d's descriptor is not a loaded neural_amd device weight", who, i);
       return nullptr;
     }
-  NadExpertBank* b = bank_new(ws.data(), n_expert, who);
+  NadExpertBank* b = bank_new(ws.data(), n_expert, who, (flags & NAD_BANK_GENERAL) != 0);
   if (!b) return nullptr;
   std::vector<GemvExpertEnt> host(static_cast<size_t>(n_expert));
   for (int i = 0; i < n_expert; i++) {
@@ -203,8 +236,8 @@ extern "C" void* nad_expert_bank_create(const void* const* weights, int n_expert
   return b;
 }
 
-extern "C" void* nad_expert_bank_plan_only(const int32_t* geom, int n_expert) {
-  const char* who = "nad_expert_bank_plan_only";
+void* bank_plan_only(const int32_t* geom, int n_expert, unsigned flags, const char* who) {
+  if (!flags_ok(flags, who)) return nullptr;
   if (!geom || n_expert < 1 || n_expert > kMaxExperts) {
     set_err("%s: need 1..%d experts (got %d)", who, kMaxExperts, n_expert);
     return nullptr;
@@ -232,7 +265,21 @@ extern "C" void* nad_expert_bank_plan_only(const int32_t* geom, int n_expert) {
     }
     ws[size_t(i)] = &w;
   }
-  return bank_new(ws.data(), n_expert, who);
+  return bank_new(ws.data(), n_expert, who, (flags & NAD_BANK_GENERAL) != 0);
+}
+}  // namespace
+
+extern "C" void* nad_expert_bank_create(const void* const* weights, int n_expert) {
+  return bank_create(weights, n_expert, 0, "nad_expert_bank_create");
+}
+extern "C" void* nad_expert_bank_create_ex(const void* const* weights, int n_expert, unsigned flags) {
+  return bank_create(weights, n_expert, flags, "nad_expert_bank_create_ex");
+}
+extern "C" void* nad_expert_bank_plan_only(const int32_t* geom, int n_expert) {
+  return bank_plan_only(geom, n_expert, 0, "nad_expert_bank_plan_only");
+}
+extern "C" void* nad_expert_bank_plan_only_ex(const int32_t* geom, int n_expert, unsigned flags) {
+  return bank_plan_only(geom, n_expert, flags, "nad_expert_bank_plan_only_ex");
 }
 
 extern "C" void nad_expert_bank_destroy(void* bank) {
@@ -247,8 +294,8 @@ extern "C" int nad_expert_bank_info(const void* bank, int64_t* out, int nout) {
   const NadExpertBank* b = as_bank(bank, "nad_expert_bank_info", "given");
   if (!b || !out || nout < 0) return -1;
   const DeviceWeight& w = b->w0;
-  const int64_t v[8] = {b->n_expert, w.bits, w.n, w.k, w.blocksize, w.scale_t, w.asym, b->dev ? 1 : 0};
-  const int c = std::min(nout, 8);
+  const int64_t v[9] = {b->n_expert, w.bits, w.n, w.k, w.blocksize, w.scale_t, w.asym, b->dev ? 1 : 0, b->kind};
+  const int c = std::min(nout, 9);
   std::memcpy(out, v, sizeof(int64_t) * size_t(c));
   return c;
 }
@@ -363,8 +410,8 @@ extern "C" int nad_plan_moe(const void* gate_bank, const void* up_bank, const vo
   if (!routed_geometry(g1, *gb, ub, kEpiSiluMul, np, who) || !routed_geometry(g2, *db, nullptr, kEpiNone, np, who))
     return -1;
   const int fout = db->w0.n;
-  const int64_t v[13] = {NAD_KERNEL_GEMV_ROUTED, g1.grid, g1.waves * 64, int64_t(g1.lds),
-                         NAD_KERNEL_GEMV_ROUTED, g2.grid, g2.waves * 64, int64_t(g2.lds),
+  const int64_t v[13] = {g1.kernel(), g1.grid, g1.waves * 64, int64_t(g1.lds),
+                         g2.kernel(), g2.grid, g2.waves * 64, int64_t(g2.lds),
                          NAD_KERNEL_MOE_COMBINE, int64_t((fout + 255) / 256) * m, 256, 0,
                          3};
   const int c = std::min(nout, 13);
@@ -414,6 +461,12 @@ GroupedWs grouped_ws(const NadExpertBank& g, const NadExpertBank* down, int m, i
 
 bool grouped_bank_ok(const NadExpertBank& b, const char* who, const char* role) {
   if (b.g7_ok) return true;
+  if (b.kind == kBankStripe) {
+    set_err("%s: the %s bank (int%d, groups of %d%s) does not take the grouped gemm7: it needs int4 groups of 32, 64 or "
+            "128 * 2^j, or int2 / int8 groups of 32 or 64 * 2^j, stripe-major, with every q * s in fp16 range",
+            who, role, b.w0.bits, b.w0.blocksize, b.w0.kmajor ? ", K-major" : "");
+    return false;
+  }
   set_err("%s: the %s bank (int%d, groups of %d%s) does not take the grouped gemm7: it needs int4 groups of 64 or 128 * 2^j, or "
           "int2 groups of 64 * 2^j, stripe-major, with every q * s in fp16 range",
           who, role, b.w0.bits, b.w0.blocksize, b.w0.kmajor ? ", K-major" : "");

@@ -102,7 +102,7 @@ __device__ __forceinline__ h8_t dequant2_fold(uint32_t x, const Dq2c& q, h2_t sc
 // separate instantiation, so the single-weight kernel keeps its code (the runtime selection in it cost 2-4 %,
 // profiles/r06_gemm7_fused_qkv_ab.txt)
 #ifdef G7_GROUPED
-// The grouped form (objects of their own: woq_gemm7_g4.o / _g2.o, G7_GROUPED; the default compilation does not see
+// The grouped form (objects of their own: woq_gemm7_g4.o / _g2.o / _g8.o, G7_GROUPED; the default compilation does not see
 // it): the same body for the sorted rows of routed experts (nad_device_moe_ffn_grouped).  Workgroup -> (tile, column
 // tile); the tile's expert and sorted row range [q0, q1) come from the device tile table the sort wrote, the weight
 // from the bank's entry of that expert, and the A rows through an optional index array (the activation row of a sorted
@@ -573,13 +573,12 @@ hipError_t launch_gemm7(const GemmArgs& a, int bits, int bm, const _Float16* A16
 }
 #endif
 
-#else  // G7_GROUPED: woq_gemm7_g4.o (int4), woq_gemm7_g2.o (int2) hold the grouped kernel and its launcher only
+#else  // G7_GROUPED: woq_gemm7_g4.o (int4), _g2.o (int2), _g8.o (int8) hold the grouped kernel and its launcher only
 // grid: column tiles x the host's tile bound (the device tile count decides which workgroups work).  lds_out set: no
 // launch, *lds_out = the dynamic LDS of the instantiation that would serve it (nad_plan_moe_grouped).
 hipError_t G7_CAT(launch_gemm7_grouped_b, G7_BITS)(const GemmArgs& a, const GemmGrouped& gg, int bm, int grid,
                                                    const _Float16* A16, int lda16, hipStream_t st, int* lds_out) {
   constexpr int BITS = G7_BITS;
-  static_assert(BITS == 4 || BITS == 2, "banks hold int4 / int2");
   const int gpt = BITS == 4 ? (a.w.bs == 32 ? 4 : (a.w.bs == 64 ? 2 : 1)) : (a.w.bs == 32 ? 2 : 1);
   auto pick = [&](auto bmc) -> hipError_t {
     constexpr int BMT = decltype(bmc)::value;
@@ -594,10 +593,15 @@ hipError_t G7_CAT(launch_gemm7_grouped_b, G7_BITS)(const GemmArgs& a, const Gemm
       return launch_big_lds<g7::woq_gemm7_grouped_kernel<BITS, BMT, AS, STT, GP>>(dim3(grid), dim3(512), LDS, st, a, A16,
                                                                                   lda16, gg);
     };
-    // what an expert bank can hold (nad_expert_bank_create takes the M = 1 GEMV's geometries): int4 groups of 64 (two
-    // per K tile) and 128 * 2^j, int2 groups of 64 * 2^j -- groups of 32 have no bank, so no instantiation here
+    // what an expert bank can hold: int4 groups of 32 (four per K tile; sym only -- int4 g32 with zero points runs on
+    // the skinny kernel at M = 1 and has no bank), of 64 (two) and of 128 * 2^j; int2 groups of 64 * 2^j; int8 groups of
+    // 32 (two per half step) and of 64 * 2^j
     auto by_gpt = [&](auto asc, auto stc) -> hipError_t {
-      if constexpr (BITS == 4) {
+      constexpr bool AS = decltype(asc)::value;
+      if constexpr (BITS == 4 && !AS) {
+        if (gpt == 4) return sel(asc, stc, std::integral_constant<int, 4>{});
+      }
+      if constexpr (BITS == 4 || BITS == 8) {
         if (gpt == 2) return sel(asc, stc, std::integral_constant<int, 2>{});
       }
       return gpt == 1 ? sel(asc, stc, std::integral_constant<int, 1>{}) : hipErrorInvalidValue;
@@ -629,11 +633,14 @@ hipError_t G7_CAT(launch_gemm7_grouped_b, G7_BITS)(const GemmArgs& a, const Gemm
 #if G7_BITS == 4
 hipError_t launch_gemm7_grouped_b2(const GemmArgs& a, const GemmGrouped& gg, int bm, int grid, const _Float16* A16,
                                    int lda16, hipStream_t st, int* lds_out);
+hipError_t launch_gemm7_grouped_b8(const GemmArgs& a, const GemmGrouped& gg, int bm, int grid, const _Float16* A16,
+                                   int lda16, hipStream_t st, int* lds_out);
 
 hipError_t launch_gemm7_grouped(const GemmArgs& a, const GemmGrouped& gg, int bits, int bm, int grid,
                                 const _Float16* A16, int lda16, hipStream_t st, int* lds_out) {
-  return bits == 2 ? launch_gemm7_grouped_b2(a, gg, bm, grid, A16, lda16, st, lds_out)
-                   : launch_gemm7_grouped_b4(a, gg, bm, grid, A16, lda16, st, lds_out);
+  return bits == 2   ? launch_gemm7_grouped_b2(a, gg, bm, grid, A16, lda16, st, lds_out)
+         : bits == 8 ? launch_gemm7_grouped_b8(a, gg, bm, grid, A16, lda16, st, lds_out)
+                     : launch_gemm7_grouped_b4(a, gg, bm, grid, A16, lda16, st, lds_out);
 }
 #endif
 #endif  // G7_GROUPED

@@ -222,7 +222,7 @@ struct GemmGrouped {
   const int32_t* ntiles;
   const int32_t* rows;        // A row of sorted row q (MoeSortArgs::src), or null: A holds the sorted rows themselves
 };
-// bits 4 / 2, bm 32 / 64 / 128 / 256 (anything else: 256), grid = tile bound * ceil(ns / 8).  lds_out set: no launch,
+// bits 4 / 2 / 8, bm 32 / 64 / 128 / 256 (anything else: 256), grid = tile bound * ceil(ns / 8).  lds_out set: no launch,
 // *lds_out = the dynamic LDS bytes of the instantiation that would serve it.
 hipError_t launch_gemm7_grouped(const GemmArgs& a, const GemmGrouped& g, int bits, int bm, int grid, const _Float16* A16,
                                 int lda16, hipStream_t stream, int* lds_out);
@@ -459,5 +459,9 @@ hipError_t launch_gemv_batch(const GemvArgs& a, int bits, int waves, int grid, s
 // the routed M = 1 launch (requires gemv_uses_m1 and fp32 activations; grid = problems * r.wpp)
 hipError_t launch_gemv_routed(const GemvArgs& a, const GemvRouted& r, int bits, int waves, int grid, size_t lds,
                               hipStream_t stream);
+// the routed stripe-stream launch (woq_gemv_routed_kernel: M = 1, fp32 activations, gemv_uses_m1 false; int4 groups of
+// 32 sym, int8 groups of 32 / 64 * 2^j / one per channel; grid = problems * r.wpp)
+hipError_t launch_gemv_routed_general(const GemvArgs& a, const GemvRouted& r, int bits, int waves, int grid, size_t lds,
+                                      hipStream_t stream);
 
 }  // namespace nad

@@ -28,6 +28,12 @@ distinct per row), three ways, alternating in one process, graph replay, HIP eve
 
 A graph holds one call on each of two layers' banks (one layer's experts are 0.7 GB int4: more than the Infinity Cache
 on their own).  A window replays the graph until it has run about --window-ms.
+
+--general: the formats only a general bank takes (ExpertBank(..., general=True): woq_gemv_routed_kernel, and the grouped
+gemm7's groups of 32 / int8) instead of the two above -- int4 g32 with fp32 scales (the reference's default
+quantization), and the layouts GGUF Q4_0 (int4 g32, fp16 scales) and Q8_0 (int8 g32, fp16 scales) load into.  The
+per-expert ffn_forward calls are then the only way the library could run these banks before; with --grouped, M = 64,
+256 and 2048.
 """
 import argparse
 import math
@@ -40,9 +46,14 @@ sys.path.insert(0, REPO)
 
 FIN, FMID, FOUT, NE, TOP_K = 4096, 14336, 4096, 8, 2
 PEAK = 8e12
-FORMATS = {
-    "int4 g128 f16": ((4, 128), (4, 128)),
-    "int2 g64 gate/up + int4 g128 down": ((2, 64), (4, 128)),
+FORMATS = {  # (bits, group, scale type) of gate / up, of down
+    "int4 g128 f16": ((4, 128, "fp16"), (4, 128, "fp16")),
+    "int2 g64 gate/up + int4 g128 down": ((2, 64, "fp16"), (4, 128, "fp16")),
+}
+GENERAL_FORMATS = {
+    "int4 g32 f32 (reference default)": ((4, 32, "fp32"), (4, 32, "fp32")),
+    "Q4_0 layout (int4 g32 f16)": ((4, 32, "fp16"), (4, 32, "fp16")),
+    "Q8_0 layout (int8 g32 f16)": ((8, 32, "fp16"), (8, 32, "fp16")),
 }
 
 
@@ -63,17 +74,20 @@ def grouped(args):
     say(f"{'format':<36}{'M':>5} {'bm':>4}  {'(a) moe_ffn_grouped us':>30}  {'(b) moe_ffn us':>32}  "
         f"{'(c) per-expert ffn_forward us':>32}  {'a/b':>6}  {'a/c':>6}  {'(a) TFLOP/s':>11}  {'a-b diff':>9}  {'a-c diff':>9}")
     L = 2
-    for name, ((gbits, ggs), (dbits, dgs)) in FORMATS.items():
-        def make(bits, n, k, gs, seed):
-            return bestla.DeviceWeight.synthetic(bits, n, k, gs, "fp16", False, seed=seed)
+    for name, ((gbits, ggs, gst), (dbits, dgs, dst)) in (GENERAL_FORMATS if args.general else FORMATS).items():
+        def make(bits, n, k, gs, st, seed):
+            return bestla.DeviceWeight.synthetic(bits, n, k, gs, st, False, seed=seed)
+
+        def bank(ws):
+            return bestla.ExpertBank(ws, general=args.general)
 
         layers = []
         for li in range(L):
-            g = [make(gbits, FMID, FIN, ggs, 1000 * li + e) for e in range(NE)]
-            u = [make(gbits, FMID, FIN, ggs, 1000 * li + 100 + e) for e in range(NE)]
-            d = [make(dbits, FOUT, FMID, dgs, 1000 * li + 200 + e) for e in range(NE)]
-            layers.append((g, u, d, bestla.ExpertBank(g), bestla.ExpertBank(u), bestla.ExpertBank(d)))
-        for m in (8, 16, 64, 256, 2048):
+            g = [make(gbits, FMID, FIN, ggs, gst, 1000 * li + e) for e in range(NE)]
+            u = [make(gbits, FMID, FIN, ggs, gst, 1000 * li + 100 + e) for e in range(NE)]
+            d = [make(dbits, FOUT, FMID, dgs, dst, 1000 * li + 200 + e) for e in range(NE)]
+            layers.append((g, u, d, bank(g), bank(u), bank(d)))
+        for m in ((64, 256, 2048) if args.general else (8, 16, 64, 256, 2048)):
             np_ = m * TOP_K
             gen = torch.Generator(device="cuda").manual_seed(m)
             x = torch.rand((m, FIN), device="cuda", generator=gen) - 0.5
@@ -175,6 +189,7 @@ def grouped(args):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--grouped", action="store_true", help="M = 16 .. 2048: grouped vs row-routed vs per-expert calls")
+    ap.add_argument("--general", action="store_true", help="the formats of general banks: int4 g32 f32, Q4_0, Q8_0")
     ap.add_argument("--window-ms", type=float, default=60.0, help="--grouped: about this much work per timed window")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--replays", type=int, default=200, help="graph replays per timed window")
@@ -198,20 +213,24 @@ def main():
         f"window, cold weights")
     say(f"{'format':<36}{'M':>3} {'L':>2} {'reps':>4}  {'(a) moe_ffn us':>28}  {'(b) per-expert ffn_forward us':>30}  "
         f"{'a/b':>5}  {'(a) us/token-layer':>18}  {'(a) of 8 TB/s':>13}  {'(b) of 8 TB/s':>13}")
-    for name, ((gbits, ggs), (dbits, dgs)) in FORMATS.items():
-        def make(bits, n, k, gs, seed):
-            return bestla.DeviceWeight.synthetic(bits, n, k, gs, "fp16", False, seed=seed)
+    for name, ((gbits, ggs, gst), (dbits, dgs, dst)) in (GENERAL_FORMATS if args.general else FORMATS).items():
+        def make(bits, n, k, gs, st, seed):
+            return bestla.DeviceWeight.synthetic(bits, n, k, gs, st, False, seed=seed)
 
-        probe = [make(gbits, FMID, FIN, ggs, 1), make(gbits, FMID, FIN, ggs, 2), make(dbits, FOUT, FMID, dgs, 3)]
+        def bank(ws):
+            return bestla.ExpertBank(ws, general=args.general)
+
+        probe = [make(gbits, FMID, FIN, ggs, gst, 1), make(gbits, FMID, FIN, ggs, gst, 2),
+                 make(dbits, FOUT, FMID, dgs, dst, 3)]
         expert_bytes = sum(w.bytes for w in probe)
         del probe
         L = max(2, math.ceil(args.gib * 2 ** 30 / (NE * expert_bytes)))
         layers = []
         for li in range(L):
-            g = [make(gbits, FMID, FIN, ggs, 1000 * li + e) for e in range(NE)]
-            u = [make(gbits, FMID, FIN, ggs, 1000 * li + 100 + e) for e in range(NE)]
-            d = [make(dbits, FOUT, FMID, dgs, 1000 * li + 200 + e) for e in range(NE)]
-            layers.append((g, u, d, bestla.ExpertBank(g), bestla.ExpertBank(u), bestla.ExpertBank(d)))
+            g = [make(gbits, FMID, FIN, ggs, gst, 1000 * li + e) for e in range(NE)]
+            u = [make(gbits, FMID, FIN, ggs, gst, 1000 * li + 100 + e) for e in range(NE)]
+            d = [make(dbits, FOUT, FMID, dgs, dst, 1000 * li + 200 + e) for e in range(NE)]
+            layers.append((g, u, d, bank(g), bank(u), bank(d)))
         reps = L * 4
         for m in (1, 4):
             x = torch.rand((m, FIN), device="cuda") - 0.5
