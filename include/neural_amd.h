@@ -398,6 +398,10 @@ int nad_device_get_rows(const void* devstor, const int32_t* ids, int ids_stride,
 #define NAD_KERNEL_GET_ROWS 20 /* woq_get_rows_kernel / woq_get_rows_q6k_kernel: ne_get_rows on a device weight */
 #define NAD_KERNEL_GEMV_ROUTED_GENERAL 21 /* woq_gemv_routed_kernel: routed expert matmuls of a general bank's int4 g32 /
                                              int8 weights on the stripe stream (nad_plan_moe) */
+#define NAD_KERNEL_Q6K_GEMV_ROUTED 22 /* woq_q6k_gemv_routed_kernel: routed expert matmuls of a bank of GGUF Q6_K experts,
+                                        one fp32 row per problem (nad_plan_moe) */
+#define NAD_KERNEL_Q6K_GEMM_GROUPED 23 /* woq_q6k_gemm_grouped_kernel: the Q6_K GEMM over the sorted rows of routed
+                                          experts, 128-row tiles (nad_plan_moe_grouped) */
 int nad_plan_get_rows(const void* devstor, int m, int out_dtype, int64_t* out, int nout);
 /* A geometry-only weight descriptor for the dry runs, no GPU needed: bits 2 / 4 / 8 (blocksize <= 0 = per-channel,
  * scale_t NAD_SCALE_*, act_order != 0: a desc_act weight) or 6 (Q6_K, k % 256 == 0; the other arguments are ignored).
@@ -458,14 +462,22 @@ void* nad_expert_bank_plan_only(const int32_t* geom, int n_expert);
  * with any scale type.  Such a bank is served by woq_gemv_routed_kernel (route kind 1) under the same contract: every
  * routed row bit-identical to the expert's own M = 1 forward, ids read on the device, one launch per matmul.  A bank
  * whose format the M = 1 stream takes is the bank the entries above make (route kind 0), whichever entry made it.
- * Still refused, by name: block mins (Q4_1 / Q5_1), Q6_K, NFloat codes, act-order, integer-compute weights, and int4
- * groups of 32 with zero points (the skinny kernel's).  The gate / up pair and the down bank of one FFN may be of
- * different kinds (Q4_0 gate / up with an int4 g128 down). */
+ * A bank whose experts are ALL GGUF Q6_K of one shape is route kind 2 (bits 6, group 16): its table entries hold the
+ * three quant pieces (tiles), d (scales) and the sub-scales (zps), and woq_q6k_gemv_routed_kernel serves it -- the
+ * dense Q6_K GEMV's body, a problem being one fp32 row, max(1, min(stripes, CUs / problems)) workgroups per problem,
+ * every routed row bit-identical to the expert's own M = 1 forward.  There an id outside [0, n_expert) reads neither
+ * weights nor activations: the row is +0.0 whatever the activations hold.  K up to 32768 (the row's hi and lo fp16
+ * images beside 32 KiB of partial sums in 160 KiB of LDS); a longer K is refused by name at the call.
+ * Still refused, by name: block mins (Q4_1 / Q5_1), a Q6_K expert beside experts of another format, a Q6_K weight in
+ * mode NAD_COMPUTE_Q8_K (integer arithmetic), NFloat codes, act-order, integer-compute weights, and int4 groups of 32
+ * with zero points (the skinny kernel's).  The gate / up pair and the down bank of one FFN may be of different kinds
+ * (Q4_0 or Q6_K gate / up with an int4 g128 down, int4 g128 gate / up with a Q6_K down). */
 #define NAD_BANK_GENERAL 1u
 void* nad_expert_bank_create_ex(const void* const* weights, int n_expert, unsigned flags);
 void* nad_expert_bank_plan_only_ex(const int32_t* geom, int n_expert, unsigned flags);
 void nad_expert_bank_destroy(void* bank);
-/* [n_expert, bits, n, k, blocksize, scale_t, asym, holds weights, route kind (0 the M = 1 stream, 1 the stripe stream)];
+/* [n_expert, bits, n, k, blocksize, scale_t, asym, holds weights, route kind (0 the M = 1 stream, 1 the stripe stream, 2 the
+ * Q6_K GEMV)];
  * writes min(nout, 9) values, returns the count or -1 */
 int nad_expert_bank_info(const void* bank, int64_t* out, int nout);
 /* ne_mul_mat_id: out[r][0:n] = act[r][0:k] . W[ids[r * ids_ld + slot]]^T for r < m, ONE launch
@@ -495,7 +507,11 @@ int nad_device_mul_mat_id(const void* bank, const float* act, const int32_t* ids
  * and up banks must agree in K, N, bits, group size, scale type and symmetry; the down bank may differ in format (the
  * int2 policy keeps it int4, llama_utils.cpp:269-287).  workspace: nad_moe_workspace_size(m, top_k, fmid, fout) = round256(m * top_k * fmid * 4) +
  * round256(m * top_k * fout * 4) bytes (round256: up to a multiple of 256), 16-byte aligned.  The window contract of
- * nad_device_mul_mat_id holds for act and out. */
+ * nad_device_mul_mat_id holds for act and out.
+ * Q6_K gate / up banks (route kind 2) run step 1 as the dense Q6_K FFN does, in two launches on the same rows of t --
+ * t[p] = act1(x_r . G_e^T), then t[p] = t[p] * (x_r . U_e^T) in place, the lane that reads an element writing it -- so
+ * the call is four launches; the workspace and the bit-identity of t[p] and y[p] are the same.  Each launch is served
+ * by its own bank's kernel, whatever the kinds of the other banks. */
 size_t nad_moe_workspace_size(int m, int top_k, int fmid, int fout);
 int nad_device_moe_ffn(const void* gate_bank, const void* up_bank, const void* down_bank, const float* act,
                        const int32_t* ids, int ids_ld, const float* wts, int wts_ld, int top_k, int epi,
@@ -510,8 +526,10 @@ int nad_moe_route(const float* logits, int ld, int m, int n_expert, int top_k, i
                   int wts_ld, void* queue);
 /* Dry run of nad_device_moe_ffn (no launch, no GPU needed; geometry-only banks qualify): per launch [kernel
  * NAD_KERNEL_*, grid, threads per workgroup, dynamic LDS bytes] -- 1 gate + up, 2 down (each NAD_KERNEL_GEMV_ROUTED, or
- * NAD_KERNEL_GEMV_ROUTED_GENERAL for a bank of route kind 1; grid = m * top_k * workgroups per problem), 3 combine -- then the launch count: 13 values.  Writes min(nout, 13),
- * returns the number written or -1. */
+ * NAD_KERNEL_GEMV_ROUTED_GENERAL for a bank of route kind 1, NAD_KERNEL_Q6K_GEMV_ROUTED for kind 2; grid = m * top_k *
+ * workgroups per problem), 3 combine -- then the launch count: 13 values.  Q6_K gate / up banks: 1 gate, 2 up, 3 down,
+ * 4 combine, then the count: 17 values.  The last value written of a full record is the launch count.  Writes
+ * min(nout, that), returns the number written or -1. */
 int nad_plan_moe(const void* gate_bank, const void* up_bank, const void* down_bank, int m, int top_k, int64_t* out,
                  int nout);
 
@@ -524,14 +542,18 @@ int nad_plan_moe(const void* gate_bank, const void* up_bank, const void* down_ba
  * A bank is taken when every expert's format is one gemm7 has (recorded at bank creation): int4 groups of 64 or
  * 128 * 2^j, int2 groups of 64 * 2^j, and for a bank of route kind 1 (NAD_BANK_GENERAL) int4 groups of 32 and int8
  * groups of 32 or 64 * 2^j, sym or asym, any
- * scale type, every q * s inside the fp16 range (geometry-only banks count as such).  The FFN also needs fmid to be a whole number of the down bank's K tiles (128
- * int4, 256 int2, 64 int8).  Anything else: -1 before any launch, nad_last_error() naming the bank and the reason -- never the
+ * scale type, every q * s inside the fp16 range (geometry-only banks count as such) -- and every bank of route kind 2
+ * (GGUF Q6_K), which woq_q6k_gemm_grouped_kernel serves: the dense Q6_K GEMM's body (128 x 128 tiles, fp16(sc * q)
+ * fragments, d applied in fp32 per superblock) with the tile -> (expert, rows) map of the sort and the weight pointers
+ * of the bank's table.  As soon as one bank of a call is Q6_K the tile height of the whole call is 128 (NAD_GEMM7_BM
+ * does not apply; gemm7's grouped kernel serves the other banks at 128).  The FFN also needs fmid to be a whole number
+ * of the down bank's K tiles (128 int4, 256 int2, 64 int8, 256 Q6_K).  Anything else: -1 before any launch, nad_last_error() naming the bank and the reason -- never the
  * row-routed path in its place.
  *
  * Arithmetic: the activations are rounded to fp16 and q * s is rounded once to fp16, as in every gemm7 forward; an
  * output element's MFMA sequence does not depend on the other rows of its tile, so y for (x_r, e) is bit-identical
  * whatever else is in the batch, whatever the tile height, and to nad_device_forward of expert e on fp16 rows where
- * that runs gemm7 without split K.  The FFN keeps act1(gate) and act1(gate) * up as fp16 (the dense prefill FFN's
+ * that runs gemm7 without split K (a Q6_K bank: where that runs woq_q6k_gemm_kernel, M > 16).  The FFN keeps act1(gate) and act1(gate) * up as fp16 (the dense prefill FFN's
  * intermediates) and y in fp32.
  *
  * Workspace (16-byte aligned, nad_moe_grouped_workspace_size bytes; np = m * top_k; every part starts at the next
@@ -542,7 +564,7 @@ int nad_plan_moe(const void* gate_bank, const void* up_bank, const void* down_ba
  *   inv   int32 [np]             the sorted position of p, -1 for an invalid id
  *   tiles int32 count, 12 bytes unused, then int32 [np / 32 + min(n_expert, np)][4] = (e, q0, q1, 0): per expert
  *         ceil(count_e / BM) tiles of at most BM sorted rows, BM the call's tile height
- *   x16   fp16 [m][kp]           the activations, kp = K rounded up to the gate bank's K tile
+ *   x16   fp16 [m][kp]           the activations, kp = K rounded up to the gate bank's K tile (Q6_K: kp = K)
  *   t16   fp16 [np][fmid]        FFN only: act1(x . G_e^T) by sorted row
  *   u16   fp16 [np][fmid]        FFN only: t16 * (x . U_e^T)
  *   y     fp32 [np][fout]        the sorted result rows (fout: the down bank's N; one matmul: the bank's N)
@@ -563,7 +585,8 @@ int nad_device_mul_mat_id_grouped(const void* bank, const float* act, const int3
                                   void* workspace, float* out, int m, int lda, int ldo, void* queue);
 /* Dry run of the grouped entries (no launch, no GPU needed; geometry-only banks qualify): per launch [kernel
  * NAD_KERNEL_*, grid, threads per workgroup, dynamic LDS bytes], then the tile height BM (gemm7's choice for m * top_k /
- * n_expert rows, or NAD_GEMM7_BM), the tile bound floor(m * top_k / BM) + min(n_expert, m * top_k) -- a grouped GEMM's
+ * n_expert rows, or NAD_GEMM7_BM; 128 with a Q6_K bank in the call, whose GEMMs are NAD_KERNEL_Q6K_GEMM_GROUPED with 512
+ * threads and static LDS, recorded as 0), the tile bound floor(m * top_k / BM) + min(n_expert, m * top_k) -- a grouped GEMM's
  * grid is that bound times its column tiles of 128 -- and the launch count.  FFN: 6 launches, 27 values; up_bank =
  * down_bank = NULL (top_k = 1): 4 launches, 19 values.  Writes min(nout, that), returns the number written or -1. */
 int nad_plan_moe_grouped(const void* gate_bank, const void* up_bank, const void* down_bank, int m, int top_k,

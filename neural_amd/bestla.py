@@ -182,7 +182,8 @@ KERNELS = {1: "woq_gemv_m1_kernel", 2: "woq_gemv_kernel", 3: "woq_skinny_kernel"
            9: "woq_gemm7_kernel", 10: "woq_mid_kernel", 11: "woq_q6k_gemv_kernel", 12: "woq_q6k_gemm_kernel",
            13: "woq_q6k_i8_kernel", 14: "woq_gemv_m1_routed_kernel", 15: "moe_combine_kernel", 16: "moe_sort_kernel",
            17: "nad_cvt_act_kernel", 18: "woq_gemm7_grouped_kernel", 19: "moe_gather_kernel",
-           20: "woq_get_rows_kernel", 21: "woq_gemv_routed_kernel"}
+           20: "woq_get_rows_kernel", 21: "woq_gemv_routed_kernel", 22: "woq_q6k_gemv_routed_kernel",
+           23: "woq_q6k_gemm_grouped_kernel"}
 
 
 def plan_forward(bits, n, k, group_size=128, scale_dtype="fp16", asym=False, m=1, act="fp32"):
@@ -684,7 +685,9 @@ class ExpertBank:
     DeviceWeights of one shape and format, held as one device table the routed kernel indexes with ids it reads on the
     device.  The weights are kept alive with the bank.  general=True (NAD_BANK_GENERAL) also takes the weights the
     stripe-stream GEMV runs at M = 1 and the M = 1 stream does not -- int4 groups of 32 sym, int8 (GGUF Q4_0, Q5_0,
-    Q8_0) -- served by woq_gemv_routed_kernel; route is 0 for the M = 1 stream, 1 for the stripe stream."""
+    Q8_0) -- served by woq_gemv_routed_kernel, and a list whose weights are all GGUF Q6_K, served by
+    woq_q6k_gemv_routed_kernel (grouped: woq_q6k_gemm_grouped_kernel); route is 0 for the M = 1 stream, 1 for the
+    stripe stream, 2 for Q6_K (bits 6, blocksize 16)."""
 
     def __init__(self, weights, general=False, _handle=None):
         self._keep = list(weights)
@@ -774,7 +777,7 @@ def moe_workspace_rows(ws, m, top_k, fmid, fout):
 
 
 def moe_ffn(gate, up, down, x, ids, wts, act="silu", out=None, stream=None, workspace=None):
-    """The routed FFN of llama.cpp:641-679 in three launches (nad_device_moe_ffn): out[r] = sum_i wts[r][i] *
+    """The routed FFN of llama.cpp:641-679 in three launches, four with Q6_K gate / up banks (nad_device_moe_ffn): out[r] = sum_i wts[r][i] *
     ((act(x_r . G_e^T) * (x_r . U_e^T)) . D_e^T), e = ids[r][i], slots summed in order.  gate / up / down: ExpertBanks;
     ids int32 [M][top_k] and wts fp32 [M][top_k] cuda tensors (row strides honoured), read on the device.  workspace: an
     fp32 cuda tensor of at least nad_moe_workspace_size bytes (moe_workspace_alloc) that no concurrent call uses; None
@@ -813,10 +816,12 @@ def moe_route(logits, top_k, stream=None):
 def plan_moe(gate, up, down, m, top_k):
     """What moe_ffn launches for m rows (nad_plan_moe: no launch, no GPU needed; plan-only banks qualify): a list of
     dict(kernel, grid, threads, lds), one per launch."""
-    o = np.zeros(13, np.int64)
-    if lib().nad_plan_moe(gate.handle, up.handle, down.handle, m, top_k, _ptr(o), 13) != 13:
+    o = np.zeros(17, np.int64)
+    c = lib().nad_plan_moe(gate.handle, up.handle, down.handle, m, top_k, _ptr(o), 17)
+    if c not in (13, 17):  # three launches, or four with Q6_K gate / up banks (gate and up apart)
         raise RuntimeError(f"nad_plan_moe failed: {last_error()}")
-    n = int(o[12])
+    n = int(o[c - 1])
+    assert c == 4 * n + 1, (c, n)
     return [dict(kernel=KERNELS.get(int(o[4 * i]), str(int(o[4 * i]))), grid=int(o[4 * i + 1]),
                  threads=int(o[4 * i + 2]), lds=int(o[4 * i + 3])) for i in range(n)]
 
@@ -847,7 +852,7 @@ def moe_grouped_workspace_rows(ws, gate, up, down, m, top_k):
     [np][fout], and for the FFN t16 / u16 fp16 [np][fmid])."""
     torch = _torch()
     np_, ne = m * top_k, gate.n_expert
-    ktile = {4: 128, 2: 256, 8: 64}[gate.bits]
+    ktile = {4: 128, 2: 256, 8: 64, 6: 256}[gate.bits]  # Q6_K: K is whole superblocks, kp = K
     kp = (gate.k + ktile - 1) // ktile * ktile
     fout = down.n if down is not None else gate.n
     o = [0]
@@ -896,7 +901,7 @@ def _check_ws(ws, need):
 
 def moe_ffn_grouped(gate, up, down, x, ids, wts, act="silu", out=None, stream=None, workspace=None):
     """moe_ffn for prefill-size M (nad_device_moe_ffn_grouped): the problems sorted by expert on the device, each
-    expert's rows through the grouped gemm7, six launches.  Same arguments as moe_ffn; workspace: a uint8 cuda tensor
+    expert's rows through the grouped gemm7 (a Q6_K bank's: woq_q6k_gemm_grouped_kernel), six launches.  Same arguments as moe_ffn; workspace: a uint8 cuda tensor
     of moe_grouped_workspace_size bytes (moe_grouped_workspace_alloc), None takes the one held for this shape and
     stream.  Banks gemm7 does not take raise (there is no fallback to moe_ffn)."""
     torch = _torch()

@@ -1,10 +1,12 @@
 // capi_moe.hip -- Mixtral-style expert FFNs with the routing read on the device (include/neural_amd.h, "routed expert
 // matmuls"): the expert bank, nad_device_mul_mat_id (ne_mul_mat_id, ne_layers.c:2384-2462, 7783-7916),
 // nad_device_moe_ffn (models/llama/llama.cpp:641-679), the router (llama.cpp:624-638) and the dry run.  The hot path is
-// woq_gemv_m1_routed_kernel, or woq_gemv_routed_kernel for a general bank's int4 g32 / int8 weights (woq_gemv.hip); the
-// bank's device table is the feature's only allocation.  For prefill
+// woq_gemv_m1_routed_kernel, or woq_gemv_routed_kernel for a general bank's int4 g32 / int8 weights (woq_gemv.hip), or
+// woq_q6k_gemv_routed_kernel for a bank of GGUF Q6_K experts (woq_q6k.hip); the bank's device table is the feature's
+// only allocation.  For prefill
 // sizes the sorted, grouped entries (nad_device_moe_ffn_grouped, nad_device_mul_mat_id_grouped): moe_sort_kernel
-// (woq_moe.hip), then woq_gemm7_grouped_kernel (woq_gemm7.hip) over every expert's sorted rows.
+// (woq_moe.hip), then woq_gemm7_grouped_kernel (woq_gemm7.hip) -- a Q6_K bank: woq_q6k_gemm_grouped_kernel -- over
+// every expert's sorted rows.
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -23,9 +25,10 @@ struct NadExpertBank {
   DeviceWeight w0{};             // the shape and format every expert shares (its pointers are expert 0's)
   GemvExpertEnt* dev = nullptr;  // [n_expert]; null for a geometry-only bank (nad_expert_bank_plan_only)
   bool g7_ok = false;            // every expert takes gemm7 (gemm7_ok, stripe-major): the grouped entries serve the bank
-  int kind = 0;                  // the routed launch that serves it: 0 the M = 1 stream, 1 the stripe stream (NAD_BANK_GENERAL)
+  int kind = 0;                  // the routed launch that serves it: 0 the M = 1 stream, 1 the stripe stream, 2 the Q6_K
+                                 // GEMV (1 and 2: NAD_BANK_GENERAL)
 };
-constexpr int kBankLean = 0, kBankStripe = 1;
+constexpr int kBankLean = 0, kBankStripe = 1, kBankQ6k = 2;
 
 const NadExpertBank* as_bank(const void* p, const char* who, const char* role) {
   const auto* b = static_cast<const NadExpertBank*>(p);
@@ -38,17 +41,21 @@ const NadExpertBank* as_bank(const void* p, const char* who, const char* role) {
 
 // nad_batch_create's conditions, per expert (the callers have checked 1 <= n <= kMaxExperts)
 // general (NAD_BANK_GENERAL): also the weights the stripe-stream GEMV runs at M = 1 where the M = 1 stream does not --
-// int4 groups of 32 sym, int8 -- with kind set to the launch that serves the bank
+// int4 groups of 32 sym, int8 -- and a bank whose experts are all GGUF Q6_K (woq_q6k_gemv_routed_kernel), with kind set
+// to the launch that serves the bank
 bool bank_check(const DeviceWeight* const* ws, int n, const char* who, bool general, int& kind) {
   const DeviceWeight& w0 = *ws[0];
   kind = kBankLean;
+  const bool q6k = general && is_q6k(w0);  // a Q6_K bank: every expert must be one (expert 0's shape and format)
   for (int i = 0; i < n; i++) {
     const DeviceWeight& w = *ws[i];
-    if (is_q6k(w)) {  // the routed GEMV streams the int4 / int2 tile layouts only
-      set_err("%s: expert %d's weight is GGUF Q6_K, which the routed GEMV does not stream", who, i);
+    if (is_q6k(w) && !q6k) {  // the routed GEMV streams the int4 / int2 (/ int8) tile layouts only
+      set_err("%s: expert %d's weight is GGUF Q6_K, which the routed GEMV does not stream%s", who, i,
+              is_q6k(w0) ? " (a bank whose experts are all Q6_K needs NAD_BANK_GENERAL)"
+                         : " beside other formats (a bank of Q6_K experts holds nothing else)");
       return false;
     }
-    if ((w.bits != 4 && w.bits != 2 && !(general && w.bits == 8)) || w.f4kind >= 0) {
+    if (!is_q6k(w) && ((w.bits != 4 && w.bits != 2 && !(general && w.bits == 8)) || w.f4kind >= 0)) {
       set_err("%s: expert %d's weight is not in the int4 / int2%s tile layout (bits %d%s)", who, i,
               general ? " / int8" : "", w.bits, w.f4kind >= 0 ? ", NFloat codes" : "");
       return false;
@@ -70,6 +77,10 @@ bool bank_check(const DeviceWeight* const* ws, int n, const char* who, bool gene
       set_err("%s: expert %d's weight carries block mins (GGUF Q4_1 / Q5_1), which are not routed", who, i);
       return false;
     }
+  }
+  if (q6k) {  // any n, any k % 256 == 0 (the loader's condition); the routed launch checks its LDS staging of K itself
+    kind = kBankQ6k;
+    return true;
   }
   GemvArgs a{};
   int waves = 0;
@@ -98,14 +109,50 @@ struct RoutedGeom {
   GemvArgs a{};
   int bits = 0, waves = 0, wpp = 0, grid = 0, kind = kBankLean;
   size_t lds = 0;
-  int kernel() const { return kind == kBankStripe ? NAD_KERNEL_GEMV_ROUTED_GENERAL : NAD_KERNEL_GEMV_ROUTED; }
+  // a Q6_K bank (kBankQ6k; a unused): the bank, and the single-weight epilogue of the launch -- none, the gate
+  // activation, or kEpiSiluMul with the problem's own output row as the multiplier (q6k_aux_out)
+  const NadExpertBank* q6k = nullptr;
+  int q6k_epi = kEpiNone;
+  bool q6k_aux_out = false;
+  int kernel() const {
+    return kind == kBankQ6k ? NAD_KERNEL_Q6K_GEMV_ROUTED
+                            : (kind == kBankStripe ? NAD_KERNEL_GEMV_ROUTED_GENERAL : NAD_KERNEL_GEMV_ROUTED);
+  }
 };
+
+// A Q6_K bank's launch: one weight per problem (the FFN runs gate and up as two launches, as the dense Q6_K FFN does)
+bool routed_geometry_q6k(RoutedGeom& g, const NadExpertBank& w, int epi, bool aux_out, int64_t nprob, const char* who) {
+  Q6kRoutedGeom q{};
+  g.kind = kBankQ6k;
+  g.bits = 6;
+  g.q6k = &w;
+  g.q6k_epi = epi;
+  g.q6k_aux_out = aux_out;
+  if (!q6k_routed_geometry(w.w0.k, w.w0.ns, nprob, device_cus(), &q)) {
+    if (q.lds > 160 * 1024)
+      set_err("%s: K = %d is too long for the routed Q6_K kernel's LDS staging of one activation row (its hi and lo "
+              "fp16 rows beside the 32 KiB of partial sums exceed 160 KiB)", who, w.w0.k);
+    else
+      set_err("%s: %lld problems are more than one launch takes", who, static_cast<long long>(nprob));
+    return false;
+  }
+  g.waves = q.waves;
+  g.wpp = q.wpp;
+  g.grid = q.grid;
+  g.lds = q.lds;
+  return true;
+}
 
 // up == nullptr: one weight per problem; else the {gate, up} pair under the dual epilogue epi.  Workgroups per
 // problem as nad_batch_create deals them: the chip's CUs over the problems, at least one, more where one problem's
 // share of the stripes would not fit a workgroup's partial-sum slots.
 bool routed_geometry(RoutedGeom& g, const NadExpertBank& w, const NadExpertBank* up, int epi, int64_t nprob,
                      const char* who) {
+  if (w.kind == kBankQ6k) {
+    if (!up) return routed_geometry_q6k(g, w, epi, false, nprob, who);
+    set_err("%s: a Q6_K pair runs as two launches", who);  // the callers do; not reached
+    return false;
+  }
   const DeviceWeight* ws[2] = {&w.w0, up ? &up->w0 : nullptr};
   g.kind = w.kind;
   if (!(g.kind == kBankStripe ? prepare_general_problem : prepare_m1_problem)(g.a, g.waves, ws, up ? 2 : 1, epi)) {
@@ -135,8 +182,26 @@ bool routed_geometry(RoutedGeom& g, const NadExpertBank& w, const NadExpertBank*
   return true;
 }
 
+SkinnyWeight bank_view(const NadExpertBank& b, float* out, int ldo);
+
 int run_routed(const RoutedGeom& g, GemvRouted r, hipStream_t st) {
   r.wpp = g.wpp;
+  if (g.kind == kBankQ6k) {
+    const DeviceWeight& w = g.q6k->w0;
+    GemmArgs a{};  // one problem: M = 1; the kernel fills A, the weight's pointers, the output row and aux
+    a.M = 1;
+    a.K = w.k;
+    a.lda = r.act_ld;
+    a.scale_t = w.scale_t;
+    a.epi = g.q6k_epi;
+    a.vec_ok = 1;  // rows_ok: a 16-B base and lda % 4 == 0 (the FFN's t rows: K = fmid, a multiple of 256)
+    a.w = bank_view(*g.q6k, nullptr, w.n);
+    const Q6kRoutedGeom q{g.wpp, g.grid, g.waves, g.lds};
+    return launch(planned(g.kernel(), g.grid, g.waves * 64), "routed Q6_K gemv kernel",
+                  [&] { return launch_q6k_gemv_routed(a, r, g.q6k_aux_out, q, st); })
+               ? 0
+               : -1;
+  }
   return launch(planned(g.kernel(), g.grid, g.waves * 64), "routed gemv kernel",
                 [&] {
                   return g.kind == kBankStripe
@@ -182,6 +247,23 @@ bool pair_ok(const NadExpertBank& g, const NadExpertBank& u, const NadExpertBank
     return false;
   }
   return true;
+}
+
+int gate_epi(int dual);
+
+// The routed launches of one FFN: g1 the {gate, up} pair under the dual epilogue -- or, for a Q6_K pair, the gate under
+// its activation alone and g1u the up weight times the gate's result in place -- and g2 the down weight.  Each launch
+// is served by its own bank's kernel.
+bool ffn_geometry(RoutedGeom& g1, RoutedGeom& g1u, RoutedGeom& g2, const NadExpertBank& gb, const NadExpertBank& ub,
+                  const NadExpertBank& db, int epi, int64_t np, const char* who) {
+  if (gb.kind == kBankQ6k) {
+    if (!routed_geometry_q6k(g1, gb, gate_epi(epi), false, np, who) ||
+        !routed_geometry_q6k(g1u, ub, kEpiSiluMul, true, np, who))
+      return false;
+  } else if (!routed_geometry(g1, gb, &ub, epi, np, who)) {
+    return false;
+  }
+  return routed_geometry(g2, db, nullptr, kEpiNone, np, who);
 }
 
 size_t ws_part(int64_t rows, int cols) { return size_t(align256(uint64_t(rows) * uint64_t(cols) * sizeof(float))); }
@@ -356,8 +438,8 @@ extern "C" int nad_device_moe_ffn(const void* gate_bank, const void* up_bank, co
   if (!rows_ok(act, lda, fin, who) || !launchable(*gb, who) || !launchable(*ub, who) || !launchable(*db, who)) return -1;
   if (m == 0) return 0;
   const int64_t np = int64_t(m) * top_k;
-  RoutedGeom g1, g2;
-  if (!routed_geometry(g1, *gb, ub, epi, np, who) || !routed_geometry(g2, *db, nullptr, kEpiNone, np, who)) return -1;
+  RoutedGeom g1, g1u, g2;
+  if (!ffn_geometry(g1, g1u, g2, *gb, *ub, *db, epi, np, who)) return -1;
   hipStream_t st = static_cast<hipStream_t>(queue);
   float* t = static_cast<float*>(workspace);                                         // [np][fmid]
   float* y = reinterpret_cast<float*>(static_cast<char*>(workspace) + ws_part(np, fmid));  // [np][fout]
@@ -367,7 +449,7 @@ extern "C" int nad_device_moe_ffn(const void* gate_bank, const void* up_bank, co
   r.ids_ld = ids_ld;
   r.ids_col = 0;
   r.slots = top_k;
-  // launch 1: t[p] = act1(x_r . G_e^T) * (x_r . U_e^T)
+  // launch 1: t[p] = act1(x_r . G_e^T) * (x_r . U_e^T); a Q6_K pair: t[p] = act1(x_r . G_e^T) alone
   r.bank[0] = gb->dev;
   r.bank[1] = ub->dev;
   r.act = act;
@@ -376,7 +458,12 @@ extern "C" int nad_device_moe_ffn(const void* gate_bank, const void* up_bank, co
   r.out = t;
   r.out_ld = fmid;
   if (run_routed(g1, r, st)) return -1;
-  // launch 2: y[p] = t[p] . D_e^T
+  if (g1.kind == kBankQ6k) {  // a Q6_K pair only, launch 1b: t[p] = t[p] * (x_r . U_e^T), in place
+    r.bank[0] = ub->dev;
+    r.bank[1] = nullptr;
+    if (run_routed(g1u, r, st)) return -1;
+  }
+  // the down launch (2; 3 after a Q6_K pair): y[p] = t[p] . D_e^T
   r.bank[0] = db->dev;
   r.bank[1] = nullptr;
   r.act = t;
@@ -385,7 +472,7 @@ extern "C" int nad_device_moe_ffn(const void* gate_bank, const void* up_bank, co
   r.out = y;
   r.out_ld = fout;
   if (run_routed(g2, r, st)) return -1;
-  // launch 3: out[r] = sum_i w[r][i] * y[r * top_k + i], in slot order
+  // the combine (3; 4 after a Q6_K pair): out[r] = sum_i w[r][i] * y[r * top_k + i], in slot order
   MoeCombineArgs c{y, fout, wts, wts_ld, top_k, out, ldo, m, fout};
   return launch(planned(NAD_KERNEL_MOE_COMBINE, ((fout + 255) / 256) * m, 256), "moe combine kernel",
                 [&] { return launch_moe_combine(c, st); })
@@ -406,15 +493,25 @@ extern "C" int nad_plan_moe(const void* gate_bank, const void* up_bank, const vo
   }
   if (!pair_ok(*gb, *ub, *db, who)) return -1;
   const int64_t np = int64_t(m) * top_k;
-  RoutedGeom g1, g2;
-  if (!routed_geometry(g1, *gb, ub, kEpiSiluMul, np, who) || !routed_geometry(g2, *db, nullptr, kEpiNone, np, who))
-    return -1;
+  RoutedGeom g1, g1u, g2;
+  if (!ffn_geometry(g1, g1u, g2, *gb, *ub, *db, kEpiSiluMul, np, who)) return -1;
   const int fout = db->w0.n;
-  const int64_t v[13] = {g1.kernel(), g1.grid, g1.waves * 64, int64_t(g1.lds),
-                         g2.kernel(), g2.grid, g2.waves * 64, int64_t(g2.lds),
-                         NAD_KERNEL_MOE_COMBINE, int64_t((fout + 255) / 256) * m, 256, 0,
-                         3};
-  const int c = std::min(nout, 13);
+  int64_t v[17];
+  int n = 0;
+  auto rec = [&](int64_t k, int64_t grid, int64_t threads, int64_t lds) {
+    v[n] = k;
+    v[n + 1] = grid;
+    v[n + 2] = threads;
+    v[n + 3] = lds;
+    n += 4;
+  };
+  rec(g1.kernel(), g1.grid, g1.waves * 64, int64_t(g1.lds));
+  if (g1.kind == kBankQ6k) rec(g1u.kernel(), g1u.grid, g1u.waves * 64, int64_t(g1u.lds));
+  rec(g2.kernel(), g2.grid, g2.waves * 64, int64_t(g2.lds));
+  rec(NAD_KERNEL_MOE_COMBINE, int64_t((fout + 255) / 256) * m, 256, 0);
+  v[n] = n / 4;
+  n++;
+  const int c = std::min(nout, n);
   std::memcpy(out, v, sizeof(int64_t) * size_t(c));
   return c;
 }
@@ -434,7 +531,7 @@ GroupedWs grouped_ws(const NadExpertBank& g, const NadExpertBank* down, int m, i
   GroupedWs w;
   w.np = int64_t(m) * top_k;
   w.bound32 = tile_bound(w.np, g.n_expert, 32);
-  w.kp = g.w0.nt * gemm7_k_tile(g.w0);
+  w.kp = g.kind == kBankQ6k ? g.w0.k : g.w0.nt * gemm7_k_tile(g.w0);  // Q6_K: K is whole superblocks, no padding
   w.fmid = down ? g.w0.n : 0;
   w.fout = down ? down->w0.n : g.w0.n;
   size_t o = 0;
@@ -460,7 +557,7 @@ GroupedWs grouped_ws(const NadExpertBank& g, const NadExpertBank* down, int m, i
 }
 
 bool grouped_bank_ok(const NadExpertBank& b, const char* who, const char* role) {
-  if (b.g7_ok) return true;
+  if (b.g7_ok || b.kind == kBankQ6k) return true;  // a Q6_K bank: woq_q6k_gemm_grouped_kernel, any shape
   if (b.kind == kBankStripe) {
     set_err("%s: the %s bank (int%d, groups of %d%s) does not take the grouped gemm7: it needs int4 groups of 32, 64 or "
             "128 * 2^j, or int2 / int8 groups of 32 or 64 * 2^j, stripe-major, with every q * s in fp16 range",
@@ -485,8 +582,11 @@ bool grouped_geometry(GroupedGeom& g, const NadExpertBank& first, const NadExper
     set_err("%s: %lld problems of these shapes are more than one launch addresses", who, static_cast<long long>(np));
     return false;
   }
-  // the height gemm7 picks for an expert's mean share of the rows
-  g.bm = gemm7_tile_height(first.w0, int((np + first.n_expert - 1) / first.n_expert));
+  // the height gemm7 picks for an expert's mean share of the rows; 128, the Q6_K kernel's one height, as soon as a
+  // bank of the call is Q6_K (NAD_GEMM7_BM does not apply: gemm7's grouped kernel has a 128 form for the other banks)
+  bool any_q6k = false;
+  for (int i = 0; i < nb; i++) any_q6k = any_q6k || banks[i]->kind == kBankQ6k;
+  g.bm = any_q6k ? 128 : gemm7_tile_height(first.w0, int((np + first.n_expert - 1) / first.n_expert));
   g.bound = tile_bound(np, first.n_expert, g.bm);
   for (int i = 0; i < nb; i++)
     if (int64_t(g.bound) * ((banks[i]->w0.ns + 7) / 8) >= (int64_t(1) << 31)) {
@@ -553,6 +653,19 @@ int run_grouped(const GroupedOp& op, const GroupedGeom& g, const GroupedPtrs& p,
   a.w = bank_view(*op.bank, op.out, w.n);
   const GemmGrouped gg{op.bank->dev, p.tiles, p.ntiles, op.rows};
   const int grid = g.bound * ((w.ns + 7) / 8);
+  if (op.bank->kind == kBankQ6k) {  // 128-row tiles (grouped_geometry), static LDS
+    if (plan4) {
+      plan4[0] = NAD_KERNEL_Q6K_GEMM_GROUPED;
+      plan4[1] = grid;
+      plan4[2] = 512;
+      plan4[3] = 0;
+      return 0;
+    }
+    a.A = op.A16;
+    a.lda = op.lda16;
+    a.vec_ok = 1;  // x16 / u16: 256-byte aligned parts of the workspace, rows of K (a multiple of 256) fp16
+    return launch(false, "grouped Q6_K gemm kernel", [&] { return launch_q6k_gemm_grouped(a, gg, grid, st); }) ? 0 : -1;
+  }
   if (plan4) {
     int lds = 0;
     (void)launch_gemm7_grouped(a, gg, w.bits, g.bm, grid, nullptr, 0, nullptr, &lds);
@@ -573,10 +686,18 @@ int gate_epi(int dual) { return dual == kEpiSiluMul ? kEpiSilu : kEpiGelu; }
 // what the FFN entry and its dry run check alike; fills ws and g
 bool grouped_ffn_ok(const NadExpertBank& gb, const NadExpertBank& ub, const NadExpertBank& db, int m, int top_k,
                     GroupedWs& ws, GroupedGeom& g, const char* who) {
+  const int fmid = gb.w0.n;
+  // ahead of pair_ok, whose "K is not N" would otherwise name the same mismatch less usefully: a Q6_K bank's K is
+  // whole superblocks, so the u16 rows it reads as they lie must be
+  if (db.kind == kBankQ6k && fmid % 256 != 0) {
+    set_err("%s: fmid (%d) is not a whole number of the Q6_K down bank's superblocks (256 deep): the fp16 "
+            "intermediate cannot be its operand as it lies", who, fmid);
+    return false;
+  }
   if (!pair_ok(gb, ub, db, who)) return false;
   if (!grouped_bank_ok(gb, who, "gate") || !grouped_bank_ok(ub, who, "up") || !grouped_bank_ok(db, who, "down"))
     return false;
-  const int fmid = gb.w0.n, kt = gemm7_k_tile(db.w0);
+  const int kt = db.kind == kBankQ6k ? 256 : gemm7_k_tile(db.w0);
   if (db.w0.nt * kt != fmid || fmid % 8 != 0) {
     set_err("%s: fmid (%d) is not a whole number of the down bank's K tiles (%d deep): the fp16 intermediate cannot be "
             "its operand as it lies", who, fmid, kt);

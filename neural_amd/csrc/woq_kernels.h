@@ -388,6 +388,21 @@ bool q6k_gemv_geometry(int m, int k, int ns, int act_t, int cus, Q6kGemvGeom* g)
 // a: A / lda / M / K, the epilogue operands and a.w (tiles = quants, zps = sub-scales, scales = d, nt = superblocks)
 hipError_t launch_q6k_gemv(const GemmArgs& a, int act_t, const Q6kGemvGeom& g, hipStream_t stream);
 hipError_t launch_q6k_gemm(const GemmArgs& a, int act_t, hipStream_t stream);  // grid: ceil(M / 128) * ceil(ns / 8)
+// Geometry of a woq_q6k_gemv_routed_kernel launch of nprob one-row problems: wpp = max(1, min(ns, cus / nprob))
+// workgroups per problem, grid = nprob * wpp, lds = 4 K (the hi and lo fp16 rows) + the 32 KiB of partials; false when
+// the two rows do not fit LDS (K > 32768) or the grid reaches 2^31
+struct Q6kRoutedGeom {
+  int wpp, grid, waves;
+  size_t lds;
+};
+bool q6k_routed_geometry(int k, int ns, int64_t nprob, int cus, Q6kRoutedGeom* g);
+// a: M = 1, K, the epilogue kind (none, SiLU / GELU, or kEpiSiluMul with aux_out: times the problem's own output row,
+// in place) and a.w -- the bank's shape; the kernel takes each problem's pointers from r (r.wpp = g.wpp)
+hipError_t launch_q6k_gemv_routed(const GemmArgs& a, const GemvRouted& r, bool aux_out, const Q6kRoutedGeom& g,
+                                  hipStream_t stream);
+// woq_q6k_gemm_grouped_kernel: a.A / a.lda the fp16 rows (gathered through gg.rows, or the sorted rows themselves), the
+// outputs by sorted row (a.out16 / a.aux16 / a.w.out); 128-row tiles, grid = tile bound * ceil(ns / 8), 512 threads
+hipError_t launch_q6k_gemm_grouped(const GemmArgs& a, const GemmGrouped& gg, int grid, hipStream_t stream);
 // quantize_row_q8_K_reference: act [m][lda] -> m rows of k/256 block_q8_K (292 bytes); k % 256 == 0
 hipError_t launch_q8_k_quant(const void* A, int act_t, int lda, int m, int k, void* blocks, hipStream_t stream);
 // Geometry of a woq_q6k_i8_kernel launch (the Q8_K integer arithmetic, any m): rows per pass (at most 16, fewer where

@@ -10,6 +10,8 @@
 // per v_mfma_f32_16x16x16_f16 -- whose K is exactly one group -- into a fresh accumulator, and applies float(sc) and
 // then d in fp32.  woq_q6k_gemm_kernel (M > 16) folds sc * q into the fragment, rounded once (<= 2^-11 relative, the
 // project's FOLD_TOL class), runs v_mfma_f32_16x16x32_f16 over two groups at a time and applies d per superblock.
+// Banks of Q6_K experts (capi_moe.hip, route kind 2) run the same two bodies with the weight taken from the bank's
+// device table: woq_q6k_gemv_routed_kernel, a problem per fp32 row, and woq_q6k_gemm_grouped_kernel over sorted rows.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -168,139 +170,66 @@ __global__ __launch_bounds__(kQ6kWaves * 64) void woq_q6k_gemv_kernel(Q6kGemvArg
   extern __shared__ __attribute__((aligned(16))) char q6k_lds[];
   constexpr bool HILO = AT != kActF16;
   const GemmArgs& a = qa.g;
-  const SkinnyWeight& W = a.w;
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave-uniform: scalar
-  const int nl = lane & 15, kq = lane >> 4;
-  const int nsb = W.nt, ns = W.ns, K = a.K;
-  const int row0 = blockIdx.y * qa.rows_pp;
-  const int mloc = min(qa.rows_pp, a.M - row0);
-  const int rows = HILO ? 2 * mloc : mloc;                         // fp16 rows in LDS
-  const size_t row_bytes = size_t(K) * 2;
-  float* part = reinterpret_cast<float*>(q6k_lds + size_t(HILO ? 2 * qa.rows_pp : qa.rows_pp) * row_bytes);
+#define Q6K_ROWS_PP (qa.rows_pp)
+#define Q6K_WG_ROW0 (blockIdx.y * qa.rows_pp)
+#define Q6K_WG_INDEX (blockIdx.x)
+#define Q6K_WG_COUNT (gridDim.x)
+#include "woq_q6k_gemv_body.inc"
+#undef Q6K_ROWS_PP
+#undef Q6K_WG_ROW0
+#undef Q6K_WG_INDEX
+#undef Q6K_WG_COUNT
+}
 
-  const u4_t* qp = static_cast<const u4_t*>(W.tiles);
-  const u4_t* scp = reinterpret_cast<const u4_t*>(W.zps);
-  const u4_t* dp = static_cast<const u4_t*>(W.scales);
-  const bool has = wave < nsb;
-  u4_t c0{}, c1{}, c2{}, csc{}, cd{};
-  auto fetch = [&](int s, int b, u4_t& l0, u4_t& l1, u4_t& h, u4_t& sc, u4_t& d) {
-    const size_t sb = size_t(s) * nsb + b;
-    const u4_t* t = qp + sb * 192 + lane;
-    l0 = __builtin_nontemporal_load(t);
-    l1 = __builtin_nontemporal_load(t + 64);
-    h = __builtin_nontemporal_load(t + 128);
-    sc = __builtin_nontemporal_load(scp + sb * 16 + nl);
-    d = __builtin_nontemporal_load(dp + sb * 2 + (nl >> 3));
-  };
-  int s = blockIdx.x;
-  if (has && s < ns) fetch(s, wave, c0, c1, c2, csc, cd);
-
-  // stage the activations: one 8-element chunk per thread and step
-  {
-    const int chunks = K / 8;
-    const bool vec_ok = a.vec_ok != 0;
-    for (int i = threadIdx.x; i < mloc * chunks; i += kQ6kWaves * 64) {
-      const int r = i / chunks, c = i % chunks;
-      float v[8];
-      load_a8<AT>(a.A, a.lda, row0 + r, c * 8, K, nullptr, vec_ok, v);
-      h8_t hi;
-#pragma unroll
-      for (int j = 0; j < 8; j++) hi[j] = _Float16(v[j]);
-      if constexpr (HILO) {
-        h8_t lo;
-#pragma unroll
-        for (int j = 0; j < 8; j++) lo[j] = _Float16(v[j] - float(hi[j]));
-        *reinterpret_cast<h8_t*>(q6k_lds + size_t(2 * r) * row_bytes + size_t(c ^ ((2 * r) & 15)) * 16) = hi;
-        *reinterpret_cast<h8_t*>(q6k_lds + size_t(2 * r + 1) * row_bytes + size_t(c ^ ((2 * r + 1) & 15)) * 16) = lo;
-      } else {
-        *reinterpret_cast<h8_t*>(q6k_lds + size_t(r) * row_bytes + size_t(c ^ (r & 15)) * 16) = hi;
-      }
-    }
+// Routed (nad_device_mul_mat_id / nad_device_moe_ffn on a bank of Q6_K experts): the same body once more, a problem
+// being one fp32 row (M = 1: its hi and its lo fp16 row).  Workgroup b serves problem p = b / wpp -- row r = p / slots,
+// slot p % slots -- and that problem's stripes b % wpp, + wpp, ...; the 16 waves own the superblocks as above and the
+// partials are summed in wave order, so a stripe's bits do not depend on wpp: a routed row has the bits of the
+// expert's own M = 1 forward.  The expert id is one wave-uniform load, clamped before the table is touched; the three
+// weight pointers come from the bank's 64-byte entry.  An id outside [0, n_expert) loads no weight and applies no
+// epilogue: the workgroup writes +0.0 to its stripes of the problem's output row and leaves before any barrier.
+// aux_out: the multiplier of the kEpiSiluMul epilogue is the problem's own output row (t = t * (x . U^T) in place: the
+// lane that reads an element is the one that writes it).
+struct Q6kRoutedArgs {
+  GemmArgs g;  // M = 1, K, the epilogue kind; w: the bank's shape (the pointers are the kernel's to fill)
+  GemvRouted r;
+  int aux_out;
+};
+__global__ __launch_bounds__(kQ6kWaves * 64) void woq_q6k_gemv_routed_kernel(Q6kRoutedArgs qa) {
+  extern __shared__ __attribute__((aligned(16))) char q6k_lds[];
+  constexpr int AT = kActF32;
+  constexpr bool HILO = true;
+  const GemvRouted& r = qa.r;
+  const int p = int(blockIdx.x) / r.wpp;
+  const int wg_index = int(blockIdx.x) - p * r.wpp, wg_count = r.wpp;
+  const int row = p / r.slots;
+  const int id = __builtin_amdgcn_readfirstlane(r.ids[size_t(row) * r.ids_ld + r.ids_col + (p - row * r.slots)]);
+  const bool valid = unsigned(id) < unsigned(r.n_expert);
+  const int e = min(max(id, 0), r.n_expert - 1);
+  float* out = r.out + size_t(p) * r.out_ld;
+  if (!valid) {
+    const int n = int(threadIdx.x);
+    for (int s = wg_index; s < qa.g.w.ns; s += r.wpp)
+      if (n < 16 && s * 16 + n < qa.g.w.n) out[s * 16 + n] = 0.f;
+    return;
   }
-  __syncthreads();
-
-  const h2_t m1056 = splat(-1056.f);
-  const f4_t zero4{0.f, 0.f, 0.f, 0.f};
-  // this lane's A fragments: row nl of LDS, four fp16 at k = 256 b + 16 g + 4 kq.  A lane past the staged rows reads
-  // row 0 instead (in bounds, finite): its row of the product is one nobody reads
-  const bool arow = nl < rows;
-  const char* abase = q6k_lds + size_t(arow ? nl : 0) * row_bytes + (kq & 1) * 8;
-  for (int it = 0; s < ns; s += gridDim.x, it++) {
-    f4_t acc = zero4;
-    if (has) {
-      for (int b = wave; b < nsb; b += kQ6kWaves) {
-        int s2 = s, b2 = b + kQ6kWaves;
-        if (b2 >= nsb) {
-          s2 = s + gridDim.x;
-          b2 = wave;
-        }
-        u4_t n0 = c0, n1 = c1, n2 = c2, nsc = csc, nd = cd;
-        if (s2 < ns) fetch(s2, b2, n0, n1, n2, nsc, nd);
-        f4_t sbacc = zero4;
-        auto group = [&](auto gc) {
-          constexpr int G = decltype(gc)::value;
-          const h4_t af = *reinterpret_cast<const h4_t*>(abase + size_t((32 * b + 2 * G + (kq >> 1)) ^ nl) * 16);
-          const f4_t p = __builtin_amdgcn_mfma_f32_16x16x16f16(af, q6k_group<G>(c0, c1, c2, m1056), zero4, 0, 0, 0);
-          const float scf = float(q6k_sc(csc, G));
-#pragma unroll
-          for (int r = 0; r < 4; r++) sbacc[r] = __builtin_fmaf(scf, p[r], sbacc[r]);
-        };
-        group(std::integral_constant<int, 0>{});
-        group(std::integral_constant<int, 1>{});
-        group(std::integral_constant<int, 2>{});
-        group(std::integral_constant<int, 3>{});
-        group(std::integral_constant<int, 4>{});
-        group(std::integral_constant<int, 5>{});
-        group(std::integral_constant<int, 6>{});
-        group(std::integral_constant<int, 7>{});
-        group(std::integral_constant<int, 8>{});
-        group(std::integral_constant<int, 9>{});
-        group(std::integral_constant<int, 10>{});
-        group(std::integral_constant<int, 11>{});
-        group(std::integral_constant<int, 12>{});
-        group(std::integral_constant<int, 13>{});
-        group(std::integral_constant<int, 14>{});
-        group(std::integral_constant<int, 15>{});
-        const float df = q6k_d(cd, nl);
-#pragma unroll
-        for (int r = 0; r < 4; r++) acc[r] = __builtin_fmaf(df, sbacc[r], acc[r]);
-        c0 = n0;
-        c1 = n1;
-        c2 = n2;
-        csc = nsc;
-        cd = nd;
-      }
-    }
-    // partial of this wave: C layout row = 4 kq + r, column nl
-    float* slot = part + size_t(it & 1) * (kQ6kWaves * 256);
-#pragma unroll
-    for (int r = 0; r < 4; r++) slot[wave * 256 + (4 * kq + r) * 16 + nl] = acc[r];
-    __syncthreads();
-    if (wave == (it & (kQ6kWaves - 1))) {
-      const int row = lane >> 2, n0 = 4 * (lane & 3);
-      float v[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll 4
-      for (int w = 0; w < kQ6kWaves; w++) {  // wave order; four reads in flight (sixteen would spill)
-        const float4 pv = *reinterpret_cast<const float4*>(slot + w * 256 + row * 16 + n0);
-        v[0] += pv.x;
-        v[1] += pv.y;
-        v[2] += pv.z;
-        v[3] += pv.w;
-      }
-      int orow = row;
-      bool valid = row < mloc;
-      if constexpr (HILO) {  // rows 2 i (hi) and 2 i + 1 (lo) sit four lanes apart
-#pragma unroll
-        for (int e = 0; e < 4; e++) {
-          const float other = __shfl_xor(v[e], 4);
-          v[e] = (row & 1) ? other + v[e] : v[e] + other;
-        }
-        orow = row >> 1;
-        valid = (row & 1) == 0 && orow < mloc;
-      }
-      if (valid && s * 16 + n0 < W.n) gemm_epilogue4(a, row0 + orow, s * 16 + n0, v);
-    }
-  }
+  const GemvExpertEnt g = r.bank[0][e];
+  GemmArgs a = qa.g;
+  a.A = r.act + size_t(r.act_per_slot ? p : row) * r.act_ld;
+  a.w.tiles = g.tiles;
+  a.w.scales = g.scales;
+  a.w.zps = g.zps;
+  a.w.out = out;
+  if (qa.aux_out) a.aux = out;
+#define Q6K_ROWS_PP 1
+#define Q6K_WG_ROW0 0
+#define Q6K_WG_INDEX (wg_index)
+#define Q6K_WG_COUNT (wg_count)
+#include "woq_q6k_gemv_body.inc"
+#undef Q6K_ROWS_PP
+#undef Q6K_WG_ROW0
+#undef Q6K_WG_INDEX
+#undef Q6K_WG_COUNT
 }
 
 bool q6k_gemv_geometry(int m, int k, int ns, int act_t, int cus, Q6kGemvGeom* g) {
@@ -325,6 +254,26 @@ hipError_t launch_q6k_gemv(const GemmArgs& a, int act_t, const Q6kGemvGeom& g, h
   return launch_big_lds<woq_q6k_gemv_kernel<kActBF16>>(grid, block, g.lds, st, qa);
 }
 
+bool q6k_routed_geometry(int k, int ns, int64_t nprob, int cus, Q6kRoutedGeom* g) {
+  g->lds = size_t(k) * 4 + kQ6kPartBytes;  // the hi and the lo fp16 row, then the partials
+  g->waves = kQ6kWaves;
+  g->wpp = g->grid = 0;
+  if (k < 256 || k % 256 != 0 || g->lds > kQ6kLdsMax || nprob < 1 || ns < 1) return false;
+  g->wpp = int(std::max<int64_t>(1, std::min<int64_t>(ns, cus / nprob)));
+  if (nprob * g->wpp >= (int64_t(1) << 31)) return false;
+  g->grid = int(nprob * g->wpp);
+  return true;
+}
+
+hipError_t launch_q6k_gemv_routed(const GemmArgs& a, const GemvRouted& r, bool aux_out, const Q6kRoutedGeom& g,
+                                  hipStream_t st) {
+  if (a.M != 1 || a.K < 256 || a.K % 256 != 0 || g.lds != size_t(a.K) * 4 + kQ6kPartBytes || g.lds > kQ6kLdsMax ||
+      r.wpp < 1 || r.wpp != g.wpp || g.grid < 1 || g.grid % r.wpp != 0 || r.n_expert < 1 || r.slots < 1)
+    return hipErrorInvalidValue;
+  Q6kRoutedArgs qa{a, r, aux_out ? 1 : 0};
+  return launch_big_lds<woq_q6k_gemv_routed_kernel>(dim3(g.grid), dim3(kQ6kWaves * 64), g.lds, st, qa);
+}
+
 // ------------------------------------------------------------------------------------------------ GEMM, M > 16
 // Register-staged MFMA tile kernel in the manner of woq_gemm_kernel (woq_kernels.hip): a 128 x 128 output tile per
 // workgroup, 8 waves as 4 (M) x 2 (N), a wave 32 rows x 4 stripes; the K step is half a superblock (128).  A goes
@@ -334,135 +283,55 @@ hipError_t launch_q6k_gemv(const GemmArgs& a, int act_t, const Q6kGemvGeom& g, h
 // matching two runs of four k.  acc_sb collects a superblock, acc += d * acc_sb in fp32.
 template <int AT>
 __global__ __launch_bounds__(512) void woq_q6k_gemm_kernel(GemmArgs a) {
-  constexpr int KT = 128, BM = 128, ROWB = KT * 2, CHUNKS = ROWB / 16;
-  __shared__ __attribute__((aligned(16))) char lds_a[BM * ROWB];
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave-uniform: scalar
-  const int wm = wave >> 1, wn = wave & 1;
-  const int nl = lane & 15, kq = lane >> 4;
-  const SkinnyWeight& W = a.w;
-  const int nbm = (a.M + BM - 1) / BM;
-  const int bn = blockIdx.x / nbm, bm = blockIdx.x % nbm;
+#define Q6K_GEMM_TILE                                      \
+  const SkinnyWeight& W = a.w;                             \
+  const int nbm = (a.M + BM - 1) / BM;                     \
+  const int bn = blockIdx.x / nbm, bm = blockIdx.x % nbm;  \
   const int m0 = bm * BM;
-  const int s0 = bn * 8 + wn * 4;
-  const int nsb = W.nt;
+#define Q6K_GEMM_M (a.M)
+#define Q6K_GEMM_A_ROWS
+#define Q6K_GEMM_A_ROW(p, row) (row)
+#include "woq_q6k_gemm_body.inc"
+#undef Q6K_GEMM_TILE
+#undef Q6K_GEMM_M
+#undef Q6K_GEMM_A_ROWS
+#undef Q6K_GEMM_A_ROW
+}
 
-  f4_t acc[2][4], accsb[2][4];
-#pragma unroll
-  for (int i = 0; i < 2; i++)
-#pragma unroll
-    for (int j = 0; j < 4; j++) acc[i][j] = accsb[i][j] = f4_t{0.f, 0.f, 0.f, 0.f};
-
-  const int ch = threadIdx.x % CHUNKS;  // 16 chunks of 8 k; 32 rows per pass, 4 passes
-  const int r0 = threadIdx.x / CHUNKS;
-  const bool vec_ok = a.vec_ok != 0;
-  const u4_t* qp = static_cast<const u4_t*>(W.tiles);
-  const u4_t* scp = reinterpret_cast<const u4_t*>(W.zps);
-  const _Float16* dp = static_cast<const _Float16*>(W.scales);
-  const h2_t m1056 = splat(-1056.f);
-
-  size_t sbi[4];  // (stripe, superblock 0) index of the wave's stripes, clamped to the last stripe
-#pragma unroll
-  for (int j = 0; j < 4; j++) sbi[j] = size_t(min(s0 + j, W.ns - 1)) * nsb;
-  u4_t lo[4], hi[4], sc[4], lo_n[4];
-#pragma unroll
-  for (int j = 0; j < 4; j++) lo[j] = qp[sbi[j] * 192 + lane];
-
-  const int nsteps = nsb * 2;
-  for (int t = 0; t < nsteps; t++) {
-    const int b = t >> 1, half = t & 1;
-#pragma unroll
-    for (int p = 0; p < 4; p++) {
-      const int r = r0 + p * 32;
-      const int row = m0 + r;
-      float v[8];
-      if (row < a.M) {
-        load_a8<AT>(a.A, a.lda, row, t * KT + ch * 8, a.K, nullptr, vec_ok, v);
-      } else {
-#pragma unroll
-        for (int j = 0; j < 8; j++) v[j] = 0.f;
-      }
-      h8_t hv;
-#pragma unroll
-      for (int j = 0; j < 8; j++) hv[j] = _Float16(v[j]);
-      *reinterpret_cast<h8_t*>(lds_a + r * ROWB + (ch ^ (r & 15)) * 16) = hv;
-    }
-    if (half == 0) {  // the superblock's crumbs and sub-scales
-#pragma unroll
-      for (int j = 0; j < 4; j++) {
-        hi[j] = qp[(sbi[j] + b) * 192 + 128 + lane];
-        sc[j] = scp[(sbi[j] + b) * 16 + nl];
-      }
-    }
-    if (t + 1 < nsteps) {
-#pragma unroll
-      for (int j = 0; j < 4; j++) lo_n[j] = qp[(sbi[j] + ((t + 1) >> 1)) * 192 + ((t + 1) & 1) * 64 + lane];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int dd = 0; dd < 4; dd++) {
-      // groups g0 = 8 half + 2 dd and g0 + 1 of the superblock: pairs 0, 1 / 2, 3 of the dword
-      h8_t bf[4];
-#pragma unroll
-      for (int j = 0; j < 4; j++) {
-        const uint32_t lw = lo[j][dd];
-        const uint32_t hw = (half ? (dd < 2 ? hi[j][2] : hi[j][3]) : (dd < 2 ? hi[j][0] : hi[j][1])) >> (8 * (dd & 1));
-        const int g0 = 8 * half + 2 * dd;
-        const h2_t s0h = splat(float(q6k_sc(sc[j], g0))), s1h = splat(float(q6k_sc(sc[j], g0 + 1)));
-        const h2_t p0 = q6k_pair(lw, q6k_hi_at4<0>(hw), m1056) * s0h;
-        const h2_t p1 = q6k_pair(lw >> 4, q6k_hi_at4<1>(hw), m1056) * s0h;
-        const h2_t p2 = q6k_pair(lw >> 8, q6k_hi_at4<2>(hw), m1056) * s1h;
-        const h2_t p3 = q6k_pair(lw >> 12, q6k_hi_at4<3>(hw), m1056) * s1h;
-        bf[j] = h8_t{p0[0], p0[1], p1[0], p1[1], p2[0], p2[1], p3[0], p3[1]};
-      }
-#pragma unroll
-      for (int i = 0; i < 2; i++) {
-        const int r = wm * 32 + i * 16 + nl;
-        // k (local) = 32 dd + 4 kq + e and + 16: chunks 4 dd + (kq >> 1) and + 2, byte (kq & 1) * 8 inside
-        const char* rp = lds_a + r * ROWB + (kq & 1) * 8;
-        const h4_t a0 = *reinterpret_cast<const h4_t*>(rp + ((4 * dd + (kq >> 1)) ^ (r & 15)) * 16);
-        const h4_t a1 = *reinterpret_cast<const h4_t*>(rp + ((4 * dd + 2 + (kq >> 1)) ^ (r & 15)) * 16);
-        const h8_t af{a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};
-#pragma unroll
-        for (int j = 0; j < 4; j++)
-          accsb[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af, bf[j], accsb[i][j], 0, 0, 0);
-      }
-    }
-    if (half == 1) {
-#pragma unroll
-      for (int j = 0; j < 4; j++) {
-        const float d = float(dp[(sbi[j] + b) * 16 + nl]);
-#pragma unroll
-        for (int i = 0; i < 2; i++) {
-#pragma unroll
-          for (int r = 0; r < 4; r++) acc[i][j][r] = __builtin_fmaf(d, accsb[i][j][r], acc[i][j][r]);
-          accsb[i][j] = f4_t{0.f, 0.f, 0.f, 0.f};
-        }
-      }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < 4; j++) lo[j] = lo_n[j];
+// Grouped (nad_device_moe_ffn_grouped / nad_device_mul_mat_id_grouped on a bank of Q6_K experts): the body above over
+// each expert's sorted rows.  Workgroup -> (tile, column tile), the column tiles of one tile in consecutive workgroups
+// as in woq_gemm7_grouped_kernel; the tile's expert and sorted rows [q0, q1), q1 - q0 <= 128, come from the table the
+// sort wrote, the weight pointers from the bank's entry of that expert.  A is fp16: rows gathered through gg.rows (the
+// activation row of a sorted row) or the sorted rows as they lie; the result goes to the sorted row.  A workgroup past
+// the device tile count leaves before any barrier.  An MFMA row depends on its own A row alone, so a sorted row's
+// bits depend neither on its tile nor on the batch: they are those of woq_q6k_gemm_kernel on that fp16 row.
+__global__ __launch_bounds__(512) void woq_q6k_gemm_grouped_kernel(GemmArgs a, GemmGrouped gg) {
+  constexpr int AT = kActF16;
+  const int nbn = (a.w.ns + 7) / 8;
+  const int tile = int(blockIdx.x) / nbn, bn = int(blockIdx.x) - tile * nbn;
+  if (tile >= __builtin_amdgcn_readfirstlane(*gg.ntiles)) return;
+  const int4 te = gg.tiles[tile];  // (expert, q0, q1, 0): q0 < q1 <= q0 + 128, expert < n_expert (the sort's contract)
+  const int m0 = __builtin_amdgcn_readfirstlane(te.y), q1 = __builtin_amdgcn_readfirstlane(te.z);
+  const GemvExpertEnt ge = gg.bank[__builtin_amdgcn_readfirstlane(te.x)];
+  SkinnyWeight Wg = a.w;
+  Wg.tiles = ge.tiles;
+  Wg.scales = ge.scales;
+  Wg.zps = ge.zps;
+#define Q6K_GEMM_TILE const SkinnyWeight& W = Wg;
+#define Q6K_GEMM_M (q1)
+  // the A rows of the thread's four tile rows, read once (a row past q1 is never loaded: it takes the last row's)
+#define Q6K_GEMM_A_ROWS                                      \
+  int asrc[4];                                               \
+  _Pragma("unroll") for (int p = 0; p < 4; p++) {            \
+    const int q = min(m0 + r0 + p * 32, q1 - 1);             \
+    asrc[p] = gg.rows ? gg.rows[q] : q;                      \
   }
-
-  // C layout: column nl, rows 4 kq + r.  gemm_epilogue4 takes four consecutive columns of a row, so the 16 x 16 tile
-  // is turned through LDS (the A tile is free after the last barrier): wave-private 1 KiB per tile
-  float* tbuf = reinterpret_cast<float*>(lds_a) + wave * 256;
-#pragma unroll
-  for (int j = 0; j < 4; j++) {
-    if (s0 + j >= W.ns) continue;
-#pragma unroll
-    for (int i = 0; i < 2; i++) {
-#pragma unroll
-      for (int r = 0; r < 4; r++) tbuf[(4 * kq + r) * 16 + nl] = acc[i][j][r];
-      __builtin_amdgcn_wave_barrier();
-      const int trow = lane >> 2, n0 = (s0 + j) * 16 + 4 * (lane & 3);
-      const float4 pv = *reinterpret_cast<const float4*>(tbuf + trow * 16 + 4 * (lane & 3));
-      float v[4] = {pv.x, pv.y, pv.z, pv.w};
-      const int row = m0 + wm * 32 + i * 16 + trow;
-      if (row < a.M && n0 < W.n) gemm_epilogue4(a, row, n0, v);
-      __builtin_amdgcn_wave_barrier();
-    }
-  }
+#define Q6K_GEMM_A_ROW(p, row) (asrc[p])
+#include "woq_q6k_gemm_body.inc"
+#undef Q6K_GEMM_TILE
+#undef Q6K_GEMM_M
+#undef Q6K_GEMM_A_ROWS
+#undef Q6K_GEMM_A_ROW
 }
 
 hipError_t launch_q6k_gemm(const GemmArgs& a, int act_t, hipStream_t st) {
@@ -474,6 +343,15 @@ hipError_t launch_q6k_gemm(const GemmArgs& a, int act_t, hipStream_t st) {
     hipLaunchKernelGGL(woq_q6k_gemm_kernel<kActF16>, grid, dim3(512), 0, st, a);
   else
     hipLaunchKernelGGL(woq_q6k_gemm_kernel<kActBF16>, grid, dim3(512), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_q6k_gemm_grouped(const GemmArgs& a, const GemmGrouped& gg, int grid, hipStream_t st) {
+  // the fp16 rows are read in 16-byte chunks: a 16-byte base and a row pitch of whole chunks
+  if (a.K < 256 || a.K % 256 != 0 || grid < 1 || !a.A || a.lda < a.K || a.lda % 8 != 0 ||
+      reinterpret_cast<uintptr_t>(a.A) % 16 != 0 || !gg.bank || !gg.tiles || !gg.ntiles)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(woq_q6k_gemm_grouped_kernel, dim3(grid), dim3(512), 0, st, a, gg);
   return hipGetLastError();
 }
 

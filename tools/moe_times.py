@@ -34,6 +34,12 @@ gemm7's groups of 32 / int8) instead of the two above -- int4 g32 with fp32 scal
 quantization), and the layouts GGUF Q4_0 (int4 g32, fp16 scales) and Q8_0 (int8 g32, fp16 scales) load into.  The
 per-expert ffn_forward calls are then the only way the library could run these banks before; with --grouped, M = 64,
 256 and 2048.
+
+--q6k: the layer with every weight GGUF Q6_K (the published model.Q6_K.gguf of Mixtral; a general bank of route kind 2:
+woq_q6k_gemv_routed_kernel, four launches per layer call, and with --grouped woq_q6k_gemm_grouped_kernel at M = 16, 64,
+256 and 2048).  The blocks are random bytes with d in 5e-6 .. 2e-5 (weights of about 1 / sqrt(K), so that the FFN's
+intermediate stays inside the fp16 range of its hi part), one array per shape loaded into every expert's own device
+memory.  (b) / (c) are again the per-expert ffn_forward calls with the ids on the host.
 """
 import argparse
 import math
@@ -50,11 +56,33 @@ FORMATS = {  # (bits, group, scale type) of gate / up, of down
     "int4 g128 f16": ((4, 128, "fp16"), (4, 128, "fp16")),
     "int2 g64 gate/up + int4 g128 down": ((2, 64, "fp16"), (4, 128, "fp16")),
 }
+Q6K_FORMATS = {"Q6_K": ((6, 16, "fp16"), (6, 16, "fp16"))}
 GENERAL_FORMATS = {
     "int4 g32 f32 (reference default)": ((4, 32, "fp32"), (4, 32, "fp32")),
     "Q4_0 layout (int4 g32 f16)": ((4, 32, "fp16"), (4, 32, "fp16")),
     "Q8_0 layout (int8 g32 f16)": ((8, 32, "fp16"), (8, 32, "fp16")),
 }
+
+
+def formats(args):
+    return Q6K_FORMATS if args.q6k else (GENERAL_FORMATS if args.general else FORMATS)
+
+
+_Q6K_BLOCKS = {}
+
+
+def make_weight(bestla, bits, n, k, gs, st, seed):
+    """a synthetic weight of the format; bits 6: Q6_K from random block bytes (made once per shape) with a finite d"""
+    if bits != 6:
+        return bestla.DeviceWeight.synthetic(bits, n, k, gs, st, False, seed=seed)
+    import numpy as np
+    if (n, k) not in _Q6K_BLOCKS:
+        rng = np.random.default_rng(n + k)
+        b = rng.integers(0, 256, size=(n, k // 256, 210), dtype=np.uint8)
+        d = rng.uniform(5e-6, 2e-5, size=(n, k // 256)).astype(np.float16)  # weights of about 1 / sqrt(K): finite t
+        b[:, :, 208:210] = d.reshape(n, k // 256, 1).view(np.uint8)
+        _Q6K_BLOCKS[(n, k)] = b.ravel()
+    return bestla.DeviceWeight.from_q6_k(_Q6K_BLOCKS[(n, k)], n, k)
 
 
 def grouped(args):
@@ -74,12 +102,12 @@ def grouped(args):
     say(f"{'format':<36}{'M':>5} {'bm':>4}  {'(a) moe_ffn_grouped us':>30}  {'(b) moe_ffn us':>32}  "
         f"{'(c) per-expert ffn_forward us':>32}  {'a/b':>6}  {'a/c':>6}  {'(a) TFLOP/s':>11}  {'a-b diff':>9}  {'a-c diff':>9}")
     L = 2
-    for name, ((gbits, ggs, gst), (dbits, dgs, dst)) in (GENERAL_FORMATS if args.general else FORMATS).items():
+    for name, ((gbits, ggs, gst), (dbits, dgs, dst)) in formats(args).items():
         def make(bits, n, k, gs, st, seed):
-            return bestla.DeviceWeight.synthetic(bits, n, k, gs, st, False, seed=seed)
+            return make_weight(bestla, bits, n, k, gs, st, seed)
 
         def bank(ws):
-            return bestla.ExpertBank(ws, general=args.general)
+            return bestla.ExpertBank(ws, general=args.general or args.q6k)
 
         layers = []
         for li in range(L):
@@ -87,7 +115,7 @@ def grouped(args):
             u = [make(gbits, FMID, FIN, ggs, gst, 1000 * li + 100 + e) for e in range(NE)]
             d = [make(dbits, FOUT, FMID, dgs, dst, 1000 * li + 200 + e) for e in range(NE)]
             layers.append((g, u, d, bank(g), bank(u), bank(d)))
-        for m in ((64, 256, 2048) if args.general else (8, 16, 64, 256, 2048)):
+        for m in ((16, 64, 256, 2048) if args.q6k else (64, 256, 2048) if args.general else (8, 16, 64, 256, 2048)):
             np_ = m * TOP_K
             gen = torch.Generator(device="cuda").manual_seed(m)
             x = torch.rand((m, FIN), device="cuda", generator=gen) - 0.5
@@ -190,6 +218,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--grouped", action="store_true", help="M = 16 .. 2048: grouped vs row-routed vs per-expert calls")
     ap.add_argument("--general", action="store_true", help="the formats of general banks: int4 g32 f32, Q4_0, Q8_0")
+    ap.add_argument("--q6k", action="store_true", help="every weight GGUF Q6_K (a general bank of route kind 2)")
     ap.add_argument("--window-ms", type=float, default=60.0, help="--grouped: about this much work per timed window")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--replays", type=int, default=200, help="graph replays per timed window")
@@ -213,12 +242,12 @@ def main():
         f"window, cold weights")
     say(f"{'format':<36}{'M':>3} {'L':>2} {'reps':>4}  {'(a) moe_ffn us':>28}  {'(b) per-expert ffn_forward us':>30}  "
         f"{'a/b':>5}  {'(a) us/token-layer':>18}  {'(a) of 8 TB/s':>13}  {'(b) of 8 TB/s':>13}")
-    for name, ((gbits, ggs, gst), (dbits, dgs, dst)) in (GENERAL_FORMATS if args.general else FORMATS).items():
+    for name, ((gbits, ggs, gst), (dbits, dgs, dst)) in formats(args).items():
         def make(bits, n, k, gs, st, seed):
-            return bestla.DeviceWeight.synthetic(bits, n, k, gs, st, False, seed=seed)
+            return make_weight(bestla, bits, n, k, gs, st, seed)
 
         def bank(ws):
-            return bestla.ExpertBank(ws, general=args.general)
+            return bestla.ExpertBank(ws, general=args.general or args.q6k)
 
         probe = [make(gbits, FMID, FIN, ggs, gst, 1), make(gbits, FMID, FIN, ggs, gst, 2),
                  make(dbits, FOUT, FMID, dgs, dst, 3)]
