@@ -85,8 +85,15 @@ extern "C" void nad_reload_knobs(void) { g_knobs = read_knobs(); }
 static thread_local NadPlan* t_plan = nullptr;
 void set_plan(NadPlan* p) { t_plan = p; }
 bool planning() { return t_plan != nullptr; }
-bool planned(int kernel, int grid, int block, int ksplit, int fold, bool main) {
+bool planned(int kernel, int grid, int block, int ksplit, int fold, bool main, size_t lds) {
   if (!t_plan) return false;
+  if (t_plan->launches < NadPlan::kListMax) {
+    int64_t* l = t_plan->list[t_plan->launches];
+    l[0] = kernel;
+    l[1] = grid;
+    l[2] = block;
+    l[3] = int64_t(lds);
+  }
   t_plan->launches++;
   if (main) {
     t_plan->kernel = kernel;

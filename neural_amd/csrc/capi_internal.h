@@ -43,13 +43,22 @@ const Knobs& knobs();
 // nad_plan_forward runs the whole host side of a forward (validation, kernel choice, geometry, workspace sizing) with
 // every launch replaced by a record of it: which kernel would serve the call, and what the host path costs per call.
 struct NadPlan {
-  int kernel = 0, grid = 0, block = 0, ksplit = 1, fold = 0, launches = 0;
+  int kernel = 0, grid = 0, block = 0, ksplit = 1, fold = 0, launches = 0;  // the last main launch; every launch counted
+  // the first kListMax launches in call order, pre-passes included: kernel code, grid, threads per workgroup, dynamic
+  // LDS bytes (the routed-expert dry runs write the list out; their longest call has 6 launches)
+  static constexpr int kListMax = 8;
+  int64_t list[kListMax][4] = {};
+  int listed() const { return launches < kListMax ? launches : kListMax; }
 };
 void set_plan(NadPlan* p);  // the calling thread's forwards record into *p until set_plan(nullptr)
 bool planning();
 // true (and the launch recorded) in a dry run; main = false for pre-passes (conversions, activation quantizers)
-bool planned(int kernel, int grid, int block, int ksplit = 1, int fold = 0, bool main = true);
+bool planned(int kernel, int grid, int block, int ksplit = 1, int fold = 0, bool main = true, size_t lds = 0);
 inline bool planned_pass() { return planned(0, 0, 0, 1, 0, false); }
+// ... of a launcher's own shape (woq_kernels.h) and its dynamic LDS
+inline bool planned(int kernel, nad::LaunchShape s, size_t lds = 0) {
+  return planned(kernel, s.grid, s.block, 1, 0, true, lds);
+}
 
 // One launch: recorded in a dry run (`recorded`, the result of planned()), else issued by fn; false, with the error
 // "<what> launch failed: ..." set, when it fails.

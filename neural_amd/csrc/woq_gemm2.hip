@@ -654,10 +654,15 @@ hipError_t launch_gemm3(const GemmArgs& a, const _Float16* A16, int lda16, hipSt
   return a.w.zps != nullptr ? by_tpg(std::true_type{}) : by_tpg(std::false_type{});
 }
 
+// a thread per 8 elements of the padded row, grid-strided past the cap
+LaunchShape cvt_act_shape(int M, int Kp) {
+  const size_t units = size_t(M) * (Kp / 8);
+  return {int(std::min<size_t>((units + 255) / 256, 4096)), 256};
+}
+
 hipError_t launch_cvt_act(const void* A, int act_t, int lda, int M, int K, int Kp, const int32_t* shuffle,
                           _Float16* out, hipStream_t st) {
-  const size_t units = size_t(M) * (Kp / 8);
-  const int blocks = int(std::min<size_t>((units + 255) / 256, 4096));
+  const int blocks = cvt_act_shape(M, Kp).grid;
   if (act_t == kActF32)
     hipLaunchKernelGGL(g2::nad_cvt_act_kernel<kActF32>, dim3(blocks), dim3(256), 0, st, A, lda, M, K, Kp, shuffle,
                        out);

@@ -575,7 +575,7 @@ hipError_t launch_gemm7(const GemmArgs& a, int bits, int bm, const _Float16* A16
 
 #else  // G7_GROUPED: woq_gemm7_g4.o (int4), _g2.o (int2), _g8.o (int8) hold the grouped kernel and its launcher only
 // grid: column tiles x the host's tile bound (the device tile count decides which workgroups work).  lds_out set: no
-// launch, *lds_out = the dynamic LDS of the instantiation that would serve it (nad_plan_moe_grouped).
+// launch, *lds_out = the dynamic LDS of the instantiation that would serve it (what a dry run records of the launch).
 hipError_t G7_CAT(launch_gemm7_grouped_b, G7_BITS)(const GemmArgs& a, const GemmGrouped& gg, int bm, int grid,
                                                    const _Float16* A16, int lda16, hipStream_t st, int* lds_out) {
   constexpr int BITS = G7_BITS;

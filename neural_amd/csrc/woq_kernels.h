@@ -174,6 +174,16 @@ struct GemvRouted {
   float* out;            // output vector of problem p: out + p * out_ld
   int out_ld;
 };
+// The grid and the threads per workgroup of a launch whose launcher owns them: the launcher takes its dim3s from the
+// *_shape function beside it, and a dry run records the same values (capi_internal.h: planned)
+struct LaunchShape {
+  int grid, block;
+};
+#pragma GCC visibility push(hidden)  // host helpers: no dynamic symbols
+LaunchShape moe_combine_shape(int m, int n);  // one workgroup per 256 columns of a row; launch_moe_gather's too
+LaunchShape moe_sort_shape();
+LaunchShape cvt_act_shape(int M, int Kp);
+#pragma GCC visibility pop
 // out[r][n] = ((w[r][0] * y[r * top_k][n]) + w[r][1] * y[r * top_k + 1][n]) + ...: separate fp32 multiplies and adds
 // in slot order (ne_mul then ne_add, llama.cpp:676-679)
 struct MoeCombineArgs {
@@ -223,7 +233,7 @@ struct GemmGrouped {
   const int32_t* rows;        // A row of sorted row q (MoeSortArgs::src), or null: A holds the sorted rows themselves
 };
 // bits 4 / 2 / 8, bm 32 / 64 / 128 / 256 (anything else: 256), grid = tile bound * ceil(ns / 8).  lds_out set: no launch,
-// *lds_out = the dynamic LDS bytes of the instantiation that would serve it.
+// *lds_out = the dynamic LDS bytes of the instantiation that would serve it (what a dry run records of the launch).
 hipError_t launch_gemm7_grouped(const GemmArgs& a, const GemmGrouped& g, int bits, int bm, int grid, const _Float16* A16,
                                 int lda16, hipStream_t stream, int* lds_out);
 // out[r][n] = ((w[r][0] * y[inv[r * top_k]][n]) + w[r][1] * y[inv[r * top_k + 1]][n]) + ... with moe_combine_kernel's

@@ -29,8 +29,10 @@ __global__ __launch_bounds__(256) void moe_combine_kernel(MoeCombineArgs a) {
   a.out[size_t(r) * a.ldo + n] = s;
 }
 
+LaunchShape moe_combine_shape(int m, int n) { return {int(unsigned((n + 255) / 256) * unsigned(m)), 256}; }
 hipError_t launch_moe_combine(const MoeCombineArgs& a, hipStream_t stream) {
-  hipLaunchKernelGGL(moe_combine_kernel, dim3(unsigned((a.n + 255) / 256) * unsigned(a.m)), dim3(256), 0, stream, a);
+  const LaunchShape s = moe_combine_shape(a.m, a.n);
+  hipLaunchKernelGGL(moe_combine_kernel, dim3(unsigned(s.grid)), dim3(s.block), 0, stream, a);
   return hipGetLastError();
 }
 
@@ -200,9 +202,11 @@ __global__ __launch_bounds__(kSortWaves * 64) void moe_sort_kernel(MoeSortArgs a
   }
 }
 
+LaunchShape moe_sort_shape() { return {1, kSortWaves * 64}; }
 hipError_t launch_moe_sort(const MoeSortArgs& a, hipStream_t stream) {
   if (a.n_expert < 1 || a.n_expert > kSortMaxE || a.bm < 1) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(moe_sort_kernel, dim3(1), dim3(kSortWaves * 64), 0, stream, a);
+  const LaunchShape s = moe_sort_shape();
+  hipLaunchKernelGGL(moe_sort_kernel, dim3(s.grid), dim3(s.block), 0, stream, a);
   return hipGetLastError();
 }
 
@@ -230,7 +234,8 @@ __global__ __launch_bounds__(256) void moe_gather_kernel(MoeGatherArgs a) {
 }
 
 hipError_t launch_moe_gather(const MoeGatherArgs& a, hipStream_t stream) {
-  hipLaunchKernelGGL(moe_gather_kernel, dim3(unsigned((a.n + 255) / 256) * unsigned(a.m)), dim3(256), 0, stream, a);
+  const LaunchShape s = moe_combine_shape(a.m, a.n);  // moe_combine_kernel's indexing
+  hipLaunchKernelGGL(moe_gather_kernel, dim3(unsigned(s.grid)), dim3(s.block), 0, stream, a);
   return hipGetLastError();
 }
 
