@@ -186,16 +186,22 @@ KERNELS = {1: "woq_gemv_m1_kernel", 2: "woq_gemv_kernel", 3: "woq_skinny_kernel"
            23: "woq_q6k_gemm_grouped_kernel"}
 
 
+_SCALE_CODE = {"fp32": 0, "bf16": 1, "fp16": 2}  # ScaleType (woq_layout.h)
+_ACT_CODE = {"fp32": 0, "fp16": 1, "bf16": 2}    # ActType: activations, and the rows get_rows writes
+
+
+def _plan6(entry, *args):
+    """One six-value dry-run entry by name, as _plan_dict."""
+    o = np.zeros(6, np.int64)
+    if getattr(lib(), entry)(*args, _ptr(o), 6) != 6:
+        raise RuntimeError(f"{entry} failed: {last_error()}")
+    return _plan_dict(o)
+
+
 def plan_forward(bits, n, k, group_size=128, scale_dtype="fp16", asym=False, m=1, act="fp32"):
     """Which kernel a forward of this geometry launches, with what grid (nad_plan_forward: the host side of the call
     with every launch recorded instead of issued -- no GPU needed)."""
-    o = np.zeros(6, np.int64)
-    st = {"fp32": 0, "bf16": 1, "fp16": 2}[scale_dtype]
-    at = {"fp32": 0, "fp16": 1, "bf16": 2}[act]
-    r = lib().nad_plan_forward(bits, n, k, group_size, st, int(asym), m, at, _ptr(o), 6)
-    if r != 6:
-        raise RuntimeError(f"nad_plan_forward failed: {last_error()}")
-    return _plan_dict(o)
+    return _plan6("nad_plan_forward", bits, n, k, group_size, _SCALE_CODE[scale_dtype], int(asym), m, _ACT_CODE[act])
 
 
 def _gemv_instance(v):
@@ -223,42 +229,25 @@ def _plan_dict(o):
 def plan_qkv_forward(bits, nq, nk, nv, k, group_size=128, scale_dtype="fp16", asym=False, m=1, act="fp32"):
     """What a fused Q/K/V forward of three weights of this format launches (nad_plan_qkv_forward: no GPU needed): the
     last main launch's kernel, grid, threads, ksplit and flags; `launches` counts every launch of the call."""
-    o = np.zeros(6, np.int64)
-    st = {"fp32": 0, "bf16": 1, "fp16": 2}[scale_dtype]
-    at = {"fp32": 0, "fp16": 1, "bf16": 2}[act]
-    if lib().nad_plan_qkv_forward(bits, nq, nk, nv, k, group_size, st, int(asym), m, at, _ptr(o), 6) != 6:
-        raise RuntimeError(f"nad_plan_qkv_forward failed: {last_error()}")
-    return _plan_dict(o)
+    return _plan6("nad_plan_qkv_forward", bits, nq, nk, nv, k, group_size, _SCALE_CODE[scale_dtype], int(asym), m,
+                  _ACT_CODE[act])
 
 
 def plan_qkv(wq, wk, wv, m, act="fp32"):
     """The same dry run for three DeviceWeights or plan_only_weight descriptors (nad_plan_qkv)."""
-    o = np.zeros(6, np.int64)
-    at = {"fp32": 0, "fp16": 1, "bf16": 2}[act]
-    wq, wk, wv = (getattr(w, "desc", w) for w in (wq, wk, wv))
-    if lib().nad_plan_qkv(wq, wk, wv, m, at, _ptr(o), 6) != 6:
-        raise RuntimeError(f"nad_plan_qkv failed: {last_error()}")
-    return _plan_dict(o)
+    return _plan6("nad_plan_qkv", *(getattr(w, "desc", w) for w in (wq, wk, wv)), m, _ACT_CODE[act])
 
 
 def plan_gate_up_forward(bits, n, k, group_size=128, scale_dtype="fp16", asym=False, m=1, act="fp32"):
     """What the FFN's fused gate/up (SiLU * mul) of two weights of this format launches (nad_plan_gate_up_forward: no
     GPU needed); the record is plan_qkv_forward's."""
-    o = np.zeros(6, np.int64)
-    st = {"fp32": 0, "bf16": 1, "fp16": 2}[scale_dtype]
-    at = {"fp32": 0, "fp16": 1, "bf16": 2}[act]
-    if lib().nad_plan_gate_up_forward(bits, n, k, group_size, st, int(asym), m, at, _ptr(o), 6) != 6:
-        raise RuntimeError(f"nad_plan_gate_up_forward failed: {last_error()}")
-    return _plan_dict(o)
+    return _plan6("nad_plan_gate_up_forward", bits, n, k, group_size, _SCALE_CODE[scale_dtype], int(asym), m,
+                  _ACT_CODE[act])
 
 
 def plan_gate_up(w1, w3, m, act="fp32"):
     """The same dry run for two loaded DeviceWeights (nad_plan_gate_up)."""
-    o = np.zeros(6, np.int64)
-    at = {"fp32": 0, "fp16": 1, "bf16": 2}[act]
-    if lib().nad_plan_gate_up(w1.desc, w3.desc, m, at, _ptr(o), 6) != 6:
-        raise RuntimeError(f"nad_plan_gate_up failed: {last_error()}")
-    return _plan_dict(o)
+    return _plan6("nad_plan_gate_up", w1.desc, w3.desc, m, _ACT_CODE[act])
 
 
 def plan_only_weight(bits, n, k, group_size=128, scale_dtype="fp16", asym=False, act_order=False):
@@ -266,17 +255,13 @@ def plan_only_weight(bits, n, k, group_size=128, scale_dtype="fp16", asym=False,
     bits 6 is GGUF Q6_K."""
     L = lib()
     desc = (C.c_uint8 * L.bestla_device_storage_size())()
-    st = {"fp32": 0, "bf16": 1, "fp16": 2}[scale_dtype]
-    check(L.nad_weight_plan_only(bits, n, k, group_size, st, int(asym), int(act_order), desc), "nad_weight_plan_only")
+    check(L.nad_weight_plan_only(bits, n, k, group_size, _SCALE_CODE[scale_dtype], int(asym), int(act_order), desc),
+          "nad_weight_plan_only")
     return desc
 
 
 def _plan_get_rows(desc, m, dtype="fp32"):
-    o = np.zeros(6, np.int64)
-    ot = {"fp32": 0, "fp16": 1, "bf16": 2}[dtype]
-    if lib().nad_plan_get_rows(desc, m, ot, _ptr(o), 6) != 6:
-        raise RuntimeError(f"nad_plan_get_rows failed: {last_error()}")
-    return _plan_dict(o)
+    return _plan6("nad_plan_get_rows", desc, m, _ACT_CODE[dtype])
 
 
 def plan_get_rows(desc, m, dtype="fp32"):
@@ -339,7 +324,7 @@ class DeviceWeight:
     def synthetic(cls, bits, n, k, group_size=128, scale_dtype="fp16", asym=False, seed=0, device=None, stream=None):
         torch = _torch()
         L = lib()
-        st = {"fp32": 0, "bf16": 1, "fp16": 2}[scale_dtype]
+        st = _SCALE_CODE[scale_dtype]
         need = L.nad_synthetic_weight_size(bits, n, k, group_size, st, int(asym))
         mem = torch.empty(need, dtype=torch.uint8, device=device or "cuda")
         desc = (C.c_uint8 * L.bestla_device_storage_size())()
@@ -442,11 +427,7 @@ class DeviceWeight:
 
     def plan(self, m, act="fp32"):
         """which kernel a forward of m rows launches (nad_plan_weight: a dry run, nothing is launched)"""
-        o = np.zeros(6, np.int64)
-        at = {"fp32": 0, "fp16": 1, "bf16": 2}[act]
-        if lib().nad_plan_weight(self.desc, m, at, _ptr(o), 6) != 6:
-            raise RuntimeError(f"nad_plan_weight failed: {last_error()}")
-        return _plan_dict(o)
+        return _plan6("nad_plan_weight", self.desc, m, _ACT_CODE[act])
 
     def get_rows(self, ids, out=None, dtype=None, stream=None):
         """ne_get_rows (nad_device_get_rows): out[r][0:k] = the dequantized weight row ids[r], bit for bit the columns
@@ -651,19 +632,13 @@ class Batch:
 
     def plan(self):
         """what run() launches (nad_plan_batch: a dry run, nothing is launched)"""
-        o = np.zeros(6, np.int64)
-        if lib().nad_plan_batch(self.handle, _ptr(o), 6) != 6:
-            raise RuntimeError(f"nad_plan_batch failed: {last_error()}")
-        return _plan_dict(o)
+        return _plan6("nad_plan_batch", self.handle)
 
     @staticmethod
     def plan_only(desc, n):
         """what a batch of n problems on this weight launches; desc: plan_only_weight's descriptor or a DeviceWeight
         (nad_plan_batch_only -- no GPU needed)"""
-        o = np.zeros(6, np.int64)
-        if lib().nad_plan_batch_only(getattr(desc, "desc", desc), n, _ptr(o), 6) != 6:
-            raise RuntimeError(f"nad_plan_batch_only failed: {last_error()}")
-        return _plan_dict(o)
+        return _plan6("nad_plan_batch_only", getattr(desc, "desc", desc), n)
 
     def __del__(self):
         h = getattr(self, "handle", None)
@@ -676,7 +651,6 @@ class Batch:
 
 
 # ---------------------------------------------------------------------------------------------------- routed experts
-_SCALE_CODE = {"fp32": 0, "bf16": 1, "fp16": 2}
 BANK_GENERAL = 1  # NAD_BANK_GENERAL
 
 

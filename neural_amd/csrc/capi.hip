@@ -1,12 +1,13 @@
 // capi.hip -- the extern "C" boundary (include/neural_amd.h): Neural Speed's BesTLA device/host/pack ABI re-hosted on
 // MI355X.  Host-side orchestration only; all arithmetic on the hot path runs in woq_kernels.hip.  This unit holds the
 // state the others share (capi_internal.h): errors, knobs, the dry-run recorder, the device context, the workspace and
-// the compute mode.  Loading is in capi_load.hip, the forwards in capi_forward.hip, the host-pointer half in
-// capi_host.hip.
+// the compute mode.  Loading is in capi_load.hip, the forwards in capi_forward.hip, their dry runs in capi_plan.hip,
+// the host-pointer half in capi_host.hip.
 #include <atomic>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <mutex>
 #include <unordered_map>
 #include <vector>
@@ -83,7 +84,15 @@ extern "C" void nad_reload_knobs(void) { g_knobs = read_knobs(); }
 
 // ------------------------------------------------------------------------------------------------ dry runs
 static thread_local NadPlan* t_plan = nullptr;
-void set_plan(NadPlan* p) { t_plan = p; }
+static void set_plan(NadPlan* p) { t_plan = p; }
+PlanScope::PlanScope() { set_plan(&plan); }
+PlanScope::~PlanScope() { set_plan(nullptr); }
+int write_plan6(const NadPlan& p, int64_t* out, int nout) {
+  const int64_t v[6] = {p.kernel, p.grid, p.block, p.ksplit, p.fold, p.launches};
+  const int c = nout < 6 ? nout : 6;
+  std::memcpy(out, v, sizeof(int64_t) * size_t(c));
+  return c;
+}
 bool planning() { return t_plan != nullptr; }
 bool planned(int kernel, int grid, int block, int ksplit, int fold, bool main, size_t lds) {
   if (!t_plan) return false;
@@ -175,6 +184,12 @@ const DeviceWeight* as_weight(const void* p) {
   }
   return w;
 }
+const DeviceWeight* any_weight(const char* who, const void* p) {
+  const auto* w = static_cast<const DeviceWeight*>(p);
+  if (w && w->magic == kWeightMagic) return w;
+  set_err("%s: weight descriptor is not a loaded neural_amd device weight", who);
+  return nullptr;
+}
 
 // ------------------------------------------------------------------------------------------------ staging
 int staging_finish(const char* who, Staging& s) {
@@ -217,7 +232,7 @@ extern "C" int nad_bind_workspace(void* queue, void* ptr, size_t bytes) {
 }
 
 void* workspace_for(size_t bytes, hipStream_t st) {
-  if (t_plan) return reinterpret_cast<void*>(uintptr_t(1) << 40);  // dry run: sized, never touched
+  if (t_plan) return stand_in<void>(kStandWorkspace);  // dry run: sized, never touched
   if (t_call_ws.ptr && t_call_ws.bytes >= bytes) return t_call_ws.ptr;
   std::lock_guard<std::mutex> lk(g_ws_mu);
   auto b = g_bound_ws.find(st);

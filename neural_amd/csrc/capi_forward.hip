@@ -1,10 +1,9 @@
 // capi_forward.hip -- the device forwards (include/neural_amd.h): kernel choice and launch geometry for decode
 // (stripe-stream GEMV, skinny), mid-M and prefill (gemm2/3/4/7), the int8 arithmetic and the GGUF min-term pass; then
-// nad_device_forward, the plan entries, the fused QKV / FFN entries and the batch API.  A call travels through the
-// internals as an Act, an Epi and an Out (capi_internal.h).
+// nad_device_forward, the fused QKV / FFN entries and the batch API (their dry runs: capi_plan.hip).  A call travels
+// through the internals as an Act, an Epi and an Out (capi_internal.h).
 #include <algorithm>
 #include <climits>
-#include <cstring>
 #include <vector>
 
 #include "capi_internal.h"
@@ -172,8 +171,8 @@ static int prepare_gemv(GemvArgs& a, int& waves, int& grid, const Act& x, const 
 // its own decode launch prepares it (capi_moe.hip: the routed launch runs every problem at exactly this geometry).  The
 // pointers in `a` are placeholders.
 static bool prepare_one_problem(GemvArgs& a, int& waves, const DeviceWeight* const* ws, int nw, int epi) {
-  const float* act = reinterpret_cast<const float*>(uintptr_t(1) << 42);  // aligned, never dereferenced on the host
-  float* y = reinterpret_cast<float*>(uintptr_t(1) << 43);
+  const float* act = stand_in<const float>(kStandAct);
+  float* y = stand_in<float>(kStandOut);
   float* outs[2] = {y, y};
   const int ldos[2] = {ws[0]->n, ws[0]->n};
   Epi e;
@@ -821,46 +820,6 @@ extern "C" void bestla_device_f32f32_forward(float* activation, void* weiptr, fl
     report("bestla_device_f32f32_forward");
 }
 
-static int plan_for(const DeviceWeight& w, int m, int act_dtype, int64_t* out, int nout) {
-  if (!out || nout < 0 || m <= 0) {
-    set_err("nad_plan_*: bad arguments (m=%d)", m);
-    return -1;
-  }
-  NadPlan plan;
-  set_plan(&plan);
-  const void* act = reinterpret_cast<const void*>(uintptr_t(1) << 42);  // aligned, never dereferenced on the host
-  float* y = reinterpret_cast<float*>(uintptr_t(1) << 43);
-  const int rc = nad_device_forward(act, act_dtype, &w, y, m, w.n, w.k, w.k, w.n, kEpiNone, nullptr, 0, nullptr, 0,
-                                    nullptr);
-  set_plan(nullptr);
-  if (rc) return -1;
-  const int64_t v[6] = {plan.kernel, plan.grid, plan.block, plan.ksplit, plan.fold, plan.launches};
-  const int c = nout < 6 ? nout : 6;
-  std::memcpy(out, v, sizeof(int64_t) * size_t(c));
-  return c;
-}
-
-extern "C" int nad_plan_forward(int bits, int n, int k, int blocksize, int scale_t, int asym, int m, int act_dtype,
-                                int64_t* out, int nout) {
-  if ((bits != 2 && bits != 4 && bits != 8) || n <= 0 || k <= 0) {
-    set_err("nad_plan_forward: bad arguments (bits=%d n=%d k=%d)", bits, n, k);
-    return -1;
-  }
-  if (blocksize <= 0) blocksize = k;
-  DeviceWeight w{};
-  layout_geometry(w, bits, n, k, blocksize, scale_t, asym != 0, false, false);
-  layout_assign(w, reinterpret_cast<void*>(uintptr_t(1) << 41));  // never dereferenced on the host
-  w.f4kind = -1;
-  w.fold_ok = 1;
-  w.owner = nullptr;
-  return plan_for(w, m, act_dtype, out, nout);
-}
-
-extern "C" int nad_plan_weight(const void* devstor, int m, int act_dtype, int64_t* out, int nout) {
-  const DeviceWeight* w = as_weight(devstor);
-  return w ? plan_for(*w, m, act_dtype, out, nout) : -1;
-}
-
 // ------------------------------------------------------------------------------------------------ fused QKV
 static bool same_kind(const DeviceWeight& a, const DeviceWeight& b) {
   return a.bits == b.bits && a.f4kind == b.f4kind && a.k == b.k && a.blocksize == b.blocksize &&
@@ -998,65 +957,6 @@ extern "C" int nad_device_qkv_forward(const void* act, int act_dtype, const void
   return 0;
 }
 
-// Dry run of nad_device_qkv_forward: every launch on that path goes through planned(), so the pointers are never
-// dereferenced.  The record is nad_plan_forward's: the last main launch, and all launches counted.
-static int plan_qkv_for(const DeviceWeight* const ws[3], int m, int act_dtype, int64_t* out, int nout) {
-  if (!out || nout < 0 || m <= 0) {
-    set_err("nad_plan_qkv*: bad arguments (m=%d)", m);
-    return -1;
-  }
-  NadPlan plan;
-  set_plan(&plan);
-  const void* act = reinterpret_cast<const void*>(uintptr_t(1) << 42);  // aligned, never dereferenced on the host
-  float* y[3];
-  for (int i = 0; i < 3; i++) y[i] = reinterpret_cast<float*>((uintptr_t(1) << 43) + (uintptr_t(i) << 38));
-  const int k = ws[0]->k;
-  const int rc = nad_device_qkv_forward(act, act_dtype, ws[0], ws[1], ws[2], y[0], y[1], y[2], m, k, k, ws[0]->n,
-                                        ws[1]->n, ws[2]->n, nullptr);
-  set_plan(nullptr);
-  if (rc) return -1;
-  const int64_t v[6] = {plan.kernel, plan.grid, plan.block, plan.ksplit, plan.fold, plan.launches};
-  const int c = nout < 6 ? nout : 6;
-  std::memcpy(out, v, sizeof(int64_t) * size_t(c));
-  return c;
-}
-
-extern "C" int nad_plan_qkv_forward(int bits, int nq, int nk, int nv, int k, int blocksize, int scale_t, int asym,
-                                    int m, int act_dtype, int64_t* out, int nout) {
-  if ((bits != 2 && bits != 4 && bits != 8) || nq <= 0 || nk <= 0 || nv <= 0 || k <= 0) {
-    set_err("nad_plan_qkv_forward: bad arguments (bits=%d n=%d,%d,%d k=%d)", bits, nq, nk, nv, k);
-    return -1;
-  }
-  if (blocksize <= 0) blocksize = k;
-  const int ns[3] = {nq, nk, nv};
-  DeviceWeight w[3] = {};
-  const DeviceWeight* ws[3];
-  for (int i = 0; i < 3; i++) {
-    layout_geometry(w[i], bits, ns[i], k, blocksize, scale_t, asym != 0, false, false);
-    layout_assign(w[i], reinterpret_cast<void*>((uintptr_t(1) << 41) + (uintptr_t(i) << 38)));  // never dereferenced
-    w[i].f4kind = -1;
-    w[i].fold_ok = 1;
-    w[i].owner = nullptr;
-    ws[i] = &w[i];
-  }
-  return plan_qkv_for(ws, m, act_dtype, out, nout);
-}
-
-// a loaded or a geometry-only (nad_weight_plan_only) weight for the dry runs of fused calls: nothing is launched on it
-static const DeviceWeight* plan_weight(const void* p) {
-  const auto* w = static_cast<const DeviceWeight*>(p);
-  if (w && w->magic == kWeightMagic) return w;
-  set_err("nad_plan_*: weight descriptor is not a neural_amd device weight");
-  return nullptr;
-}
-
-extern "C" int nad_plan_qkv(const void* wq, const void* wk, const void* wv, int m, int act_dtype, int64_t* out,
-                            int nout) {
-  const DeviceWeight* ws[3] = {plan_weight(wq), plan_weight(wk), plan_weight(wv)};
-  if (!ws[0] || !ws[1] || !ws[2]) return -1;
-  return plan_qkv_for(ws, m, act_dtype, out, nout);
-}
-
 // ------------------------------------------------------------------------------------------------ fused FFN
 // The gate/up half of the fused FFN (ip_fusion_ffn.cpp:407-433): tmp2 = act(X.W1^T) * (X.W3^T), tmp1 = act(X.W1^T)
 // (optional at M <= 16, required above).  Decode: one dual-weight stream launch; prefill: two GEMM launches.
@@ -1125,52 +1025,6 @@ extern "C" int nad_device_ffn_gate_up(const void* act, int act_dtype, const void
   }
   if (run_gemm(x, *w1, Out{tmp1, fmid}, Epi::gate_of(epi), st, pp)) return -1;
   return run_gemm(x, *w3, up, Epi::mul(tmp1, fmid), st, pp);
-}
-
-// Dry run of nad_device_ffn_gate_up (SiLU * mul, with the tmp1 output): the record is nad_plan_forward's.
-static int plan_gate_up_for(const DeviceWeight& w1, const DeviceWeight& w3, int m, int act_dtype, int64_t* out,
-                            int nout) {
-  if (!out || nout < 0 || m <= 0) {
-    set_err("nad_plan_gate_up*: bad arguments (m=%d)", m);
-    return -1;
-  }
-  NadPlan plan;
-  set_plan(&plan);
-  const void* act = reinterpret_cast<const void*>(uintptr_t(1) << 42);  // aligned, never dereferenced on the host
-  float* t1 = reinterpret_cast<float*>(uintptr_t(1) << 43);
-  float* t2 = reinterpret_cast<float*>((uintptr_t(1) << 43) + (uintptr_t(1) << 38));
-  const int rc = nad_device_ffn_gate_up(act, act_dtype, &w1, &w3, t1, t2, m, w1.k, w1.n, w1.k, kEpiSiluMul, nullptr);
-  set_plan(nullptr);
-  if (rc) return -1;
-  const int64_t v[6] = {plan.kernel, plan.grid, plan.block, plan.ksplit, plan.fold, plan.launches};
-  const int c = nout < 6 ? nout : 6;
-  std::memcpy(out, v, sizeof(int64_t) * size_t(c));
-  return c;
-}
-
-extern "C" int nad_plan_gate_up_forward(int bits, int n, int k, int blocksize, int scale_t, int asym, int m,
-                                        int act_dtype, int64_t* out, int nout) {
-  if ((bits != 2 && bits != 4 && bits != 8) || n <= 0 || k <= 0) {
-    set_err("nad_plan_gate_up_forward: bad arguments (bits=%d n=%d k=%d)", bits, n, k);
-    return -1;
-  }
-  if (blocksize <= 0) blocksize = k;
-  DeviceWeight w[2] = {};
-  for (int i = 0; i < 2; i++) {
-    layout_geometry(w[i], bits, n, k, blocksize, scale_t, asym != 0, false, false);
-    layout_assign(w[i], reinterpret_cast<void*>((uintptr_t(1) << 41) + (uintptr_t(i) << 38)));  // never dereferenced
-    w[i].f4kind = -1;
-    w[i].fold_ok = 1;
-    w[i].owner = nullptr;
-  }
-  return plan_gate_up_for(w[0], w[1], m, act_dtype, out, nout);
-}
-
-extern "C" int nad_plan_gate_up(const void* w1p, const void* w3p, int m, int act_dtype, int64_t* out, int nout) {
-  const DeviceWeight* w1 = plan_weight(w1p);
-  const DeviceWeight* w3 = plan_weight(w3p);
-  if (!w1 || !w3) return -1;
-  return plan_gate_up_for(*w1, *w3, m, act_dtype, out, nout);
 }
 
 int ffn_forward(const void* act, int act_dtype, const void* w1p, const void* w2p, const void* w3p, float* tmp1,
@@ -1298,7 +1152,7 @@ extern "C" void* nad_batch_create(const nad_batch_problem* p, int n) {
     host[i] = GemvBatchEnt{p[i].act, w->tiles, w->scales, w->zps, p[i].out, {nullptr, nullptr, nullptr}};
   }
   if (planning()) {  // nad_plan_batch_only: geometry-only weights, no table; nad_batch_run only records
-    b->a.batch = reinterpret_cast<const GemvBatchEnt*>(uintptr_t(1) << 44);
+    b->a.batch = stand_in<const GemvBatchEnt>(kStandTable);
     return b;
   }
   if (hipMalloc(&b->dev, sizeof(GemvBatchEnt) * size_t(n)) != hipSuccess ||
@@ -1320,50 +1174,6 @@ extern "C" int nad_batch_run(void* batch, void* queue) {
          })
              ? 0
              : -1;
-}
-
-// Dry run of nad_batch_run: the record of nad_plan_forward (the batched launch has no specialised or load-ahead form),
-// the instantiation named by launch_gemv_batch's own launch statement.
-extern "C" int nad_plan_batch(void* batch, int64_t* out, int nout) {
-  if (!batch || !out || nout < 0) {
-    set_err("nad_plan_batch: bad arguments");
-    return -1;
-  }
-  NadPlan plan;
-  set_plan(&plan);
-  const int rc = nad_batch_run(batch, nullptr);
-  set_plan(nullptr);
-  if (rc) return -1;
-  const int64_t v[6] = {plan.kernel, plan.grid, plan.block, plan.ksplit, plan.fold, plan.launches};
-  const int c = nout < 6 ? nout : 6;
-  std::memcpy(out, v, sizeof(int64_t) * size_t(c));
-  return c;
-}
-
-// The same dry run for n problems on a loaded or geometry-only (nad_weight_plan_only) weight, no GPU needed: the batch
-// is created without its device table, recorded and destroyed.
-extern "C" int nad_plan_batch_only(const void* devstor, int n, int64_t* out, int nout) {
-  if (!devstor || n <= 0 || !out || nout < 0) {
-    set_err("nad_plan_batch_only: bad arguments");
-    return -1;
-  }
-  std::vector<nad_batch_problem> p(static_cast<size_t>(n));
-  for (auto& q : p) {
-    q.weight = devstor;
-    q.act = reinterpret_cast<const float*>(uintptr_t(1) << 42);  // aligned, never dereferenced on the host
-    q.out = reinterpret_cast<float*>(uintptr_t(1) << 43);
-  }
-  NadPlan plan;
-  set_plan(&plan);
-  void* b = nad_batch_create(p.data(), n);
-  const int rc = b ? nad_batch_run(b, nullptr) : -1;
-  set_plan(nullptr);
-  nad_batch_destroy(b);
-  if (rc) return -1;
-  const int64_t v[6] = {plan.kernel, plan.grid, plan.block, plan.ksplit, plan.fold, plan.launches};
-  const int c = nout < 6 ? nout : 6;
-  std::memcpy(out, v, sizeof(int64_t) * size_t(c));
-  return c;
 }
 
 extern "C" void nad_batch_destroy(void* batch) {

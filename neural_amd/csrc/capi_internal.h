@@ -1,6 +1,6 @@
-// capi_internal.h -- what the units behind the extern "C" boundary share: capi.hip (errors, knobs, dry runs, device
-// context, workspace, compute mode), capi_load.hip, capi_forward.hip, capi_host.hip, capi_moe.hip.  Nothing here is
-// exported.
+// capi_internal.h -- what the units behind the extern "C" boundary share: capi.hip (errors, knobs, the dry-run
+// recorder, device context, workspace, compute mode), capi_load.hip, capi_forward.hip, capi_plan.hip (the dense dry
+// runs), capi_host.hip, capi_moe.hip, capi_quant.hip, capi_rows.hip.  Nothing here is exported.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -50,7 +50,27 @@ struct NadPlan {
   int64_t list[kListMax][4] = {};
   int listed() const { return launches < kListMax ? launches : kListMax; }
 };
-void set_plan(NadPlan* p);  // the calling thread's forwards record into *p until set_plan(nullptr)
+// The calling thread's forwards record into `plan` for as long as the scope lives, however it is left.
+struct PlanScope {
+  NadPlan plan;
+  PlanScope();
+  ~PlanScope();
+  PlanScope(const PlanScope&) = delete;
+  PlanScope& operator=(const PlanScope&) = delete;
+};
+// A dry run: body (an entry's own, on stand-in arguments) with its launches recorded; -1 if it fails, else what
+// write(plan) returns.  write_plan6 is the dense entries' writer: kernel, grid, block, ksplit, fold, launches, the
+// first min(nout, 6) of them, and that count returned.
+template <class F, class W>
+static inline int dry_run(F&& body, W&& write) {
+  PlanScope s;
+  return body() ? -1 : write(s.plan);
+}
+int write_plan6(const NadPlan& p, int64_t* out, int nout);
+template <class F>
+static inline int dry_run6(int64_t* out, int nout, F&& body) {
+  return dry_run(body, [&](const NadPlan& p) { return write_plan6(p, out, nout); });
+}
 bool planning();
 // true (and the launch recorded) in a dry run; main = false for pre-passes (conversions, activation quantizers)
 bool planned(int kernel, int grid, int block, int ksplit = 1, int fold = 0, bool main = true, size_t lds = 0);
@@ -89,7 +109,10 @@ struct NadDevice {
   bool profile;
 };
 
-const nad::DeviceWeight* as_weight(const void* p);  // null, with the error set, for anything but a loaded weight
+// null, with the error set, for anything but a loaded weight -- or, inside a dry run, a geometry-only one
+const nad::DeviceWeight* as_weight(const void* p);
+// a loaded or a geometry-only weight, outside a dry run too ("<who>: weight descriptor is not a loaded ...")
+const nad::DeviceWeight* any_weight(const char* who, const void* p);
 
 // ------------------------------------------------------------------------------------------------ workspace (capi.hip)
 void* workspace_for(size_t bytes, hipStream_t st);
@@ -108,6 +131,52 @@ inline bool is_q6k(const nad::DeviceWeight& w) { return w.bits == 6; }
 int gguf_act_quant(const nad::DeviceWeight& w);
 bool int8_compute(const nad::DeviceWeight& w);  // a forward of this weight takes the int8 arithmetic right now
 bool q8k_compute(const nad::DeviceWeight& w);   // a Q6_K weight set to NAD_COMPUTE_Q8_K: forward_q6k takes woq_q6k_i8_kernel
+
+// ------------------------------------------------------------------------------------------------ dry-run stand-ins
+// The addresses a dry run passes where a call takes device memory: aligned, distinct, never dereferenced on the host.
+// Role r starts at 2^(42 + r) and holds one 2^38-byte slot per object -- at most 4, where the workspace's range ends
+// and the weights' begins -- so no two overlap:
+//   2^40  the workspace of the dense forwards (workspace_for)
+//   2^41  weight sections, slot i the call's i-th weight (plan_weight_assign)
+//   2^42  activations
+//   2^43  outputs, slot i the call's i-th (QKV, gate / up); a routed call's expert ids
+//   2^44  the batch table (nad_batch_create); a routed call's combine weights
+//   2^45, 2^46  a routed call's workspace and output (capi_moe.hip takes both from its caller)
+// The 16-byte alignment of the activation address feeds vec_aligned and a_fast, and so the kernel choice.
+enum StandIn {
+  kStandWorkspace = -2, kStandWeight = -1, kStandAct = 0, kStandOut = 1, kStandTable = 2,
+  kStandMoeIds = 1, kStandMoeWts = 2, kStandMoeWorkspace = 3, kStandMoeOut = 4
+};
+template <class T>
+static inline T* stand_in(int role, int slot = 0) {
+  return reinterpret_cast<T*>((uintptr_t(1) << (42 + role)) + (uintptr_t(slot) << 38));
+}
+
+// A weight made from scalars for the dry runs, in two steps: the geometry (bits = 6: GGUF Q6_K; blocksize is the
+// caller's, already resolved) with every pointer null -- which is what marks a descriptor as geometry-only
+// (nad_weight_plan_only stops here) -- then stand-in section pointers for the call's i-th weight.  An integer weight
+// may fold its scales (fold_ok, which a load checks over the scales); the Q6_K kernels do not read the flag.
+inline bool plan_geometry_ok(int bits, int n, int k, int scale_t) {
+  return n > 0 && k > 0 && (bits == 2 || bits == 4 || bits == 6 || bits == 8) && (bits != 6 || k % 256 == 0) &&
+         scale_t >= nad::kScaleF32 && scale_t <= nad::kScaleF16;
+}
+inline void plan_weight_geometry(nad::DeviceWeight& w, int bits, int n, int k, int blocksize, int scale_t, int asym,
+                                 int act_order) {
+  if (bits == 6) {
+    nad::q6k_geometry(w, n, k);
+    return;
+  }
+  w = nad::DeviceWeight{};
+  nad::layout_geometry(w, bits, n, k, blocksize, scale_t, asym != 0, act_order != 0, false);
+  w.fold_ok = 1;
+}
+inline void plan_weight_assign(nad::DeviceWeight& w, int i) {
+  void* base = stand_in<void>(kStandWeight, i);
+  if (is_q6k(w))
+    nad::q6k_assign(w, base);
+  else
+    nad::layout_assign(w, base);
+}
 
 // ------------------------------------------------------------------------------------------------ staging (capi.hip)
 struct HipStagingApi {
@@ -198,6 +267,10 @@ bool prepare_general_problem(nad::GemvArgs& a, int& waves, const nad::DeviceWeig
 // ... and the tile height a gemm7 launch of m rows on w takes (NAD_GEMM7_BM, else the cost model), and w's K tile
 int gemm7_tile_height(const nad::DeviceWeight& w, int m);
 int gemm7_k_tile(const nad::DeviceWeight& w);
+
+// capi_rows.hip, for its dry run in capi_plan.hip: nad_device_get_rows under the name `who` in its error texts
+int get_rows(const char* who, const void* devstor, const int32_t* ids, int ids_stride, int m, void* out, int out_dtype,
+             int ldo, hipStream_t st);
 
 #pragma GCC visibility pop
 

@@ -1,8 +1,9 @@
 // capi_moe.hip -- Mixtral-style expert FFNs with the routing read on the device (include/neural_amd.h, "routed expert
 // matmuls"): the expert bank, nad_device_mul_mat_id (ne_mul_mat_id, ne_layers.c:2384-2462, 7783-7916),
 // nad_device_moe_ffn (models/llama/llama.cpp:641-679), the router (llama.cpp:624-638) and the dry runs.  A dry run
-// (nad_plan_moe, nad_plan_moe_grouped) is the entry's own body run on stand-in arguments under set_plan: every launch
-// statement records itself instead of launching (capi_internal.h: planned), and the record is written out.
+// (nad_plan_moe, nad_plan_moe_grouped) is the entry's own body run on stand-in arguments under the launch recorder
+// (capi_internal.h: dry_run): every launch statement records itself instead of launching (planned), and the record is
+// written out.
 // The hot path is woq_gemv_m1_routed_kernel, or woq_gemv_routed_kernel for a general bank's int4 g32 / int8 weights
 // (woq_gemv.hip), or woq_q6k_gemv_routed_kernel for a bank of GGUF Q6_K experts (woq_q6k.hip); the bank's device table
 // is the feature's only allocation.  For prefill sizes the sorted, grouped entries (nad_device_moe_ffn_grouped,
@@ -340,21 +341,12 @@ void* bank_plan_only(const int32_t* geom, int n_expert, unsigned flags, const ch
     const int32_t* g = geom + 6 * i;
     const int bits = g[0], n = g[1], k = g[2], asym = g[5];
     DeviceWeight& w = store[size_t(i)];
-    if (n <= 0 || k <= 0 || (bits != 2 && bits != 4 && bits != 6 && bits != 8) || (bits == 6 && k % 256 != 0) ||
-        g[4] < kScaleF32 || g[4] > kScaleF16) {
+    if (!plan_geometry_ok(bits, n, k, g[4])) {
       set_err("%s: expert %d: bad geometry (bits=%d n=%d k=%d scale=%d)", who, i, bits, n, k, g[4]);
       return nullptr;
     }
-    void* fake = reinterpret_cast<void*>(uintptr_t(1) << 41);  // never dereferenced on the host
-    if (bits == 6) {
-      q6k_geometry(w, n, k);
-      q6k_assign(w, fake);
-    } else {
-      w = DeviceWeight{};
-      layout_geometry(w, bits, n, k, g[3] <= 0 ? k : g[3], g[4], asym != 0, false, false);
-      layout_assign(w, fake);
-      w.fold_ok = 1;
-    }
+    plan_weight_geometry(w, bits, n, k, g[3] <= 0 ? k : g[3], g[4], asym, 0);
+    plan_weight_assign(w, 0);  // every expert on slot 0: only the bank's geometry is read
     ws[size_t(i)] = &w;
   }
   return bank_new(ws.data(), n_expert, who, (flags & NAD_BANK_GENERAL) != 0);
@@ -652,36 +644,29 @@ int mul_mat_id_grouped(const void* bank, const float* act, const int32_t* ids, i
 }
 
 // ------------------------------------------------------------------------------------------------ the dry runs
-// Stand-in arguments (plan_for, capi_forward.hip): aligned addresses that are never dereferenced on the host; rows of K
-// rounded up to a multiple of 4 floats, ids and weights of top_k columns, the output of the down bank's N
-template <class T>
-T* stand_in(int i) {
-  return reinterpret_cast<T*>(uintptr_t(1) << (42 + i));
-}
+// Stand-in arguments (capi_internal.h: stand_in): rows of K rounded up to a multiple of 4 floats, ids and weights of
+// top_k columns, the output of the down bank's N
 int padded4(int k) { return (k + 3) / 4 * 4; }
 FfnCall stand_in_call(const FfnBanks& b, int m, int top_k) {
-  return FfnCall{b.g, b.u, b.d, stand_in<const float>(0), stand_in<const int32_t>(1), top_k, stand_in<const float>(2),
-                 top_k, top_k, kEpiSiluMul, stand_in<void>(3), stand_in<float>(4), m, padded4(b.g->w0.k), b.d->w0.n,
-                 nullptr};
+  return FfnCall{b.g, b.u, b.d, stand_in<const float>(kStandAct), stand_in<const int32_t>(kStandMoeIds), top_k,
+                 stand_in<const float>(kStandMoeWts), top_k, top_k, kEpiSiluMul, stand_in<void>(kStandMoeWorkspace),
+                 stand_in<float>(kStandMoeOut), m, padded4(b.g->w0.k), b.d->w0.n, nullptr};
 }
 
-// Runs body (an entry's, on stand-ins) with its launches recorded, then writes the record out: four values per launch
-// (kernel code, grid, threads, dynamic LDS bytes), the ntail values body left in tail, the launch count
+// The routed dry runs' writer (capi_internal.h: dry_run): four values per launch (kernel code, grid, threads, dynamic
+// LDS bytes), the ntail values body left in tail, the launch count
 template <class F>
-int dry_run(int64_t* out, int nout, const int64_t* tail, int ntail, F&& body) {
-  NadPlan plan;
-  set_plan(&plan);
-  const int rc = body();
-  set_plan(nullptr);
-  if (rc) return -1;
-  int64_t v[4 * NadPlan::kListMax + 3];
-  int n = 4 * plan.listed();
-  std::memcpy(v, plan.list, sizeof(int64_t) * size_t(n));
-  for (int i = 0; i < ntail; i++) v[n++] = tail[i];
-  v[n++] = plan.listed();
-  const int c = std::min(nout, n);
-  std::memcpy(out, v, sizeof(int64_t) * size_t(c));
-  return c;
+int dry_run_list(int64_t* out, int nout, const int64_t* tail, int ntail, F&& body) {
+  return dry_run(body, [&](const NadPlan& plan) {
+    int64_t v[4 * NadPlan::kListMax + 3];
+    int n = 4 * plan.listed();
+    std::memcpy(v, plan.list, sizeof(int64_t) * size_t(n));
+    for (int i = 0; i < ntail; i++) v[n++] = tail[i];
+    v[n++] = plan.listed();
+    const int c = std::min(nout, n);
+    std::memcpy(out, v, sizeof(int64_t) * size_t(c));
+    return c;
+  });
 }
 }  // namespace
 
@@ -756,7 +741,7 @@ extern "C" int nad_plan_moe(const void* gate_bank, const void* up_bank, const vo
     set_err("%s: bad arguments (m=%d top_k=%d)", who, m, top_k);
     return -1;
   }
-  return dry_run(out, nout, nullptr, 0, [&] { return moe_ffn(stand_in_call(b, m, top_k), who); });
+  return dry_run_list(out, nout, nullptr, 0, [&] { return moe_ffn(stand_in_call(b, m, top_k), who); });
 }
 
 extern "C" size_t nad_moe_grouped_workspace_size(const void* gate_bank, const void* up_bank, const void* down_bank,
@@ -800,12 +785,12 @@ extern "C" int nad_plan_moe_grouped(const void* gate_bank, const void* up_bank, 
     return -1;
   }
   int64_t geom[2] = {0, 0};  // the tile height and the tile bound, from the body's own GroupedGeom
-  return dry_run(out, nout, geom, 2, [&] {
+  return dry_run_list(out, nout, geom, 2, [&] {
     GroupedGeom g;
     const int rc = ffn ? moe_ffn_grouped(stand_in_call(b, m, top_k), g, who)
-                       : mul_mat_id_grouped(b.g, stand_in<const float>(0), stand_in<const int32_t>(1), 1, 0,
-                                            stand_in<void>(3), stand_in<float>(4), m, padded4(b.g->w0.k), b.g->w0.n,
-                                            nullptr, g, who);
+                       : mul_mat_id_grouped(b.g, stand_in<const float>(kStandAct), stand_in<const int32_t>(kStandMoeIds),
+                                            1, 0, stand_in<void>(kStandMoeWorkspace), stand_in<float>(kStandMoeOut), m,
+                                            padded4(b.g->w0.k), b.g->w0.n, nullptr, g, who);
     geom[0] = g.bm;
     geom[1] = g.bound;
     return rc;

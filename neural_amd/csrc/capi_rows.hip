@@ -1,24 +1,15 @@
-// capi_rows.hip -- ne_get_rows on a device weight (include/neural_amd.h): nad_device_get_rows, its dry run, and the
-// geometry-only descriptor the dry runs of a single weight take without a GPU.
+// capi_rows.hip -- ne_get_rows on a device weight (include/neural_amd.h): nad_device_get_rows (its dry run,
+// nad_plan_get_rows, is in capi_plan.hip).
 #include <climits>
-#include <cstring>
 
 #include "capi_internal.h"
 #include "woq_rows.h"
 
 using namespace nad;
 
-namespace {
-// a loaded or a geometry-only weight (as_weight refuses the latter outside a dry run; here the argument checks come
-// first and the launch is refused below)
-const DeviceWeight* any_weight(const char* who, const void* p) {
-  const auto* w = static_cast<const DeviceWeight*>(p);
-  if (w && w->magic == kWeightMagic) return w;
-  set_err("%s: weight descriptor is not a loaded neural_amd device weight", who);
-  return nullptr;
-}
-
-// the checks in the order the header states them, the geometry, then the launch or its record
+// the checks in the order the header states them, the geometry, then the launch or its record.  The weight may be
+// geometry-only (any_weight: as_weight refuses that outside a dry run; here the argument checks come first and the
+// launch is refused below)
 int get_rows(const char* who, const void* devstor, const int32_t* ids, int ids_stride, int m, void* out, int out_dtype,
              int ldo, hipStream_t st) {
   const DeviceWeight* w = any_weight(who, devstor);
@@ -88,56 +79,9 @@ int get_rows(const char* who, const void* devstor, const int32_t* ids, int ids_s
   a.bs32 = (q6k || w->ng <= 1) ? INT_MAX : w->blocksize / 32;
   return launch(rec, "row gather kernel", [&] { return launch_get_rows(a, grid, st); }) ? 0 : -1;
 }
-}  // namespace
 
 extern "C" int nad_device_get_rows(const void* devstor, const int32_t* ids, int ids_stride, int m, void* out,
                                    int out_dtype, int ldo, void* queue) {
   return get_rows("nad_device_get_rows", devstor, ids, ids_stride, m, out, out_dtype, ldo,
                   static_cast<hipStream_t>(queue));
-}
-
-extern "C" int nad_plan_get_rows(const void* devstor, int m, int out_dtype, int64_t* out, int nout) {
-  const char* who = "nad_plan_get_rows";
-  if (!out || nout < 0) {
-    set_err("%s: no output buffer", who);
-    return -1;
-  }
-  const DeviceWeight* w = any_weight(who, devstor);
-  if (!w) return -1;
-  NadPlan plan;
-  set_plan(&plan);
-  void* y = reinterpret_cast<void*>(uintptr_t(1) << 43);  // aligned, never dereferenced on the host
-  const int ldo = (w->k + 7) & ~7;
-  const int rc = get_rows(who, devstor, nullptr, 1, m, y, out_dtype, ldo, nullptr);
-  set_plan(nullptr);
-  if (rc) return -1;
-  const int64_t v[6] = {plan.kernel, plan.grid, plan.block, plan.ksplit, plan.fold, plan.launches};
-  const int c = nout < 6 ? nout : 6;
-  std::memcpy(out, v, sizeof(int64_t) * size_t(c));
-  return c;
-}
-
-extern "C" int nad_weight_plan_only(int bits, int n, int k, int blocksize, int scale_t, int asym, int act_order,
-                                    void* devstor) {
-  const char* who = "nad_weight_plan_only";
-  if (!devstor || n <= 0 || k <= 0 || (bits != 2 && bits != 4 && bits != 6 && bits != 8) || (bits == 6 && k % 256 != 0) ||
-      scale_t < kScaleF32 || scale_t > kScaleF16) {
-    set_err("%s: bad geometry (bits=%d n=%d k=%d scale=%d)", who, bits, n, k, scale_t);
-    return -1;
-  }
-  if (blocksize <= 0 || blocksize > k) blocksize = k;
-  if (bits != 6 && blocksize % 32 && blocksize < k) {
-    set_err("%s: group size must be a multiple of 32", who);
-    return -1;
-  }
-  DeviceWeight w{};
-  if (bits == 6) {
-    q6k_geometry(w, n, k);
-  } else {
-    layout_geometry(w, bits, n, k, blocksize, scale_t, asym != 0, act_order != 0, false);
-    w.fold_ok = 1;
-  }
-  // no layout_assign: every pointer stays null, which is what marks the descriptor as holding no weights
-  std::memcpy(devstor, &w, sizeof(w));
-  return 0;
 }
