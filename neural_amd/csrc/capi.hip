@@ -113,8 +113,11 @@ bool planned(int kernel, int grid, int block, int ksplit, int fold, bool main, s
   }
   return true;
 }
+// the name, and from it flag bit 4 (woq_gemv_m1s_kernel: family 3) and bit 8 (its load-ahead order)
 void plan_gemv_instance(uint32_t inst) {
-  if (t_plan) t_plan->fold |= int(inst) << nad::kPlanGemvInstShift;
+  if (!t_plan) return;
+  const int m1s = (inst & 3u) == 3u ? 4 : 0, ahead = (inst >> 24 & 1u) ? 8 : 0;
+  t_plan->fold |= m1s | ahead | int(inst) << nad::kPlanGemvInstShift;
 }
 
 // ------------------------------------------------------------------------------------------------ device context

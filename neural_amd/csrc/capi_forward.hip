@@ -102,7 +102,7 @@ int device_cus() {
 }
 
 // ------------------------------------------------------------------------------------------------ decode: GEMV, skinny
-// Fill the GemvArgs, waves and grid of one decode op on the persistent stripe-stream GEMV (woq_gemv.hip); returns 1
+// Fill the GemvArgs, waves and grid of one decode op on the persistent stripe-stream GEMV (woq_gemv.h); returns 1
 // when that kernel handles it, 0 when not eligible: M <= 16, the staged activations fit LDS, the group size tiles the K
 // tile, and all weights share one act-order LUT.
 static int prepare_gemv(GemvArgs& a, int& waves, int& grid, const Act& x, const Weights& W, const Epi& e,
@@ -196,8 +196,7 @@ static int try_gemv(const Act& x, const Weights& W, const Epi& e, hipStream_t st
   if (!prepare_gemv(a, waves, grid, x, W, e)) return 0;
   const int bits = W[0].bits;
   const size_t lds = gemv_lds_layout(a, bits, waves, grid);
-  const bool dry = planned(gemv_uses_m1(a, bits, waves) ? NAD_KERNEL_GEMV_M1 : NAD_KERNEL_GEMV, grid, waves * 64, 1,
-                           !planning() ? 0 : (gemv_uses_m1s(a, bits, waves) ? 4 : 0) | (gemv_uses_ahead(a, bits, waves) ? 8 : 0));
+  const bool dry = planned(gemv_uses_m1(a, bits, waves) ? NAD_KERNEL_GEMV_M1 : NAD_KERNEL_GEMV, grid, waves * 64, 1, 0);
   return launch_gemv_named(dry, "gemv kernel", [&] { return launch_gemv(a, bits, waves, grid, lds, st); }) ? 1 : -1;
 }
 
@@ -423,7 +422,6 @@ static int pipelined_gemm(const DeviceWeight& w, int m) {
   return 0;
 }
 static bool gemm2_ok(const DeviceWeight& w, int m) { return pipelined_gemm(w, m) != 0; }
-static int k_tile(const DeviceWeight& w) { return w.bits == 4 ? 128 : (w.bits == 2 ? 256 : 64); }
 // The FFN's prefill keeps its intermediates in fp16 when all three GEMMs are the pipelined ones reading the unshuffled
 // fp16 operand and fmid is a whole number of w2's K tiles (NAD_FFN_F32=1: the fp32 intermediates, A/B)
 static bool ffn16_ok(const DeviceWeight& w1, const DeviceWeight& w2, const DeviceWeight& w3, int m, int fmid) {
@@ -431,12 +429,12 @@ static bool ffn16_ok(const DeviceWeight& w1, const DeviceWeight& w2, const Devic
     return pipelined_gemm(w, m) && !w.shuffle && !int8_compute(w);
   };
   return !knobs().ffn_f32 && knobs().gemm_kernel != 2 && ok(w1) && ok(w2) && ok(w3) &&
-         w2.nt * k_tile(w2) == fmid && fmid % 8 == 0;
+         w2.nt * tile_k(w2.bits) == fmid && fmid % 8 == 0;
 }
 
 // 1 ready, -1 error (no workspace under capture, launch error)
 static int prepare_a16(A16& r, const Act& x, const DeviceWeight& w, hipStream_t st) {
-  const int kp = w.nt * k_tile(w);
+  const int kp = w.nt * tile_k(w.bits);
   r.kp = kp;
   if (x.t == kActF16 && !w.shuffle && x.k == kp && reinterpret_cast<uintptr_t>(x.p) % 16 == 0 &&
       (size_t(x.ld) * 2) % 16 == 0) {
@@ -462,7 +460,7 @@ static int splitk_plan(const DeviceWeight& w, int m, int* ktiles, int bm = 256) 
   if (knobs().splitk_disable) return 1;
   const int tiles = ((m + bm - 1) / bm) * ((w.ns + 7) / 8);
   if (tiles > 128) return 1;
-  const int tpg = std::max(1, w.blocksize / k_tile(w));
+  const int tpg = std::max(1, w.blocksize / tile_k(w.bits));
   const int unit = tpg >= 2 ? tpg : 2;  // K tiles per run at least: one whole group and two tiles
   int s = std::min(256 / tiles, w.nt / unit);
   if (s < 2) return 1;
@@ -584,7 +582,7 @@ static int gemm7_pick_bm(const DeviceWeight& w, int m) {
   static const int bms[3] = {64, 128, 256};
   static const double hs_us[3] = {0.35, 0.55, 0.95}, fixed_us[3] = {5.5, 5.0, 8.0};
   const int cus = device_cus();
-  const int hpt = k_tile(w) / 64;
+  const int hpt = tile_k(w.bits) / 64;
   int best = 256;
   double best_t = 1e30;
   for (int i = 0; i < 3; i++) {
@@ -611,7 +609,7 @@ static int gemm7_bm(const DeviceWeight& w, int m) {
   return (bm != 32 && bm != 64 && bm != 128) ? 256 : bm;
 }
 int gemm7_tile_height(const DeviceWeight& w, int m) { return gemm7_bm(w, m); }
-int gemm7_k_tile(const DeviceWeight& w) { return k_tile(w); }
+int gemm7_k_tile(const DeviceWeight& w) { return tile_k(w.bits); }
 
 // M > 16, one weight: the int8 arithmetic, the mid-M kernel, a pipelined GEMM on the fp16 activations (pre: a copy the
 // caller shares among weights) or the register-staged fallback
@@ -647,7 +645,7 @@ static int run_gemm(const Act& x, const DeviceWeight& w, const Out& o, const Epi
   // round at K = 4096 (4096 x 4096, 256 tiles; profiles/r04_gemm4_ksw_ab.txt): auto picks it for the former
   if (pg == 4 && a.fold) {
     const int tiles = ((m + 255) / 256) * ((w.n + 127) / 128);
-    const bool win = tiles > device_cus() || w.nt * k_tile(w) >= 8192;
+    const bool win = tiles > device_cus() || w.nt * tile_k(w.bits) >= 8192;
     a.ksw = kn.gemm4_ksw == 1 || (kn.gemm4_ksw == 2 && win) ? 1 : 0;
   }
   if (o.h16 && !pg) {
@@ -659,7 +657,7 @@ static int run_gemm(const Act& x, const DeviceWeight& w, const Out& o, const Epi
     return launch(planned(NAD_KERNEL_GEMM, 0, 0), "gemm kernel", [&] { return launch_gemm(a, w.bits, x.t, st); }) ? 0
                                                                                                                  : -1;
   A16 own;
-  if (!pre || pre->kp != w.nt * k_tile(w) || w.shuffle) {
+  if (!pre || pre->kp != w.nt * tile_k(w.bits) || w.shuffle) {
     if (prepare_a16(own, x, w, st) < 0) return -1;
     pre = &own;
   }
@@ -674,7 +672,7 @@ static int run_gemm(const Act& x, const DeviceWeight& w, const Out& o, const Epi
   const int ks = !g2 ? splitk_plan(w, m, &ktiles, bm) : 1;
   if (ks > 1 && kn.gemm4_ksw == 2) a.ksw = 0;  // auto KSW was measured on whole-K launches only
   // partials after the fp16 activations
-  if (ks > 1 && !splitk_slabs(a, w, m, ks, ktiles, (size_t(m) * w.nt * k_tile(w) * 2 + 255) / 256 * 256, st)) return -1;
+  if (ks > 1 && !splitk_slabs(a, w, m, ks, ktiles, (size_t(m) * w.nt * tile_k(w.bits) * 2 + 255) / 256 * 256, st)) return -1;
   const int tiles = ((m + bm - 1) / bm) * ((w.n + 127) / 128);
   // split K: every run of a tile and the reduce of its slabs on one XCD (slabs read back from that XCD's L2): K = N =
   // 4096 M = 128 18.6 -> 15.9 us, M = 96 17.2 -> 14.8 (profiles/r06_gemm7_xcd_splitk_ab.txt)
@@ -867,7 +865,7 @@ static int run_gemm7_fused(const Act& x, const Weights& W, hipStream_t st, const
   a.nwt = n;
   if (planned(NAD_KERNEL_GEMM7, ((m + bm0 - 1) / bm0) * cut, 512, 1, 1)) return 1;
   A16 own;
-  if (!pre || pre->kp != W[0].nt * k_tile(W[0])) {
+  if (!pre || pre->kp != W[0].nt * tile_k(W[0].bits)) {
     if (prepare_a16(own, x, W[0], st) < 0) return -1;
     pre = &own;
   }
@@ -949,7 +947,7 @@ extern "C" int nad_device_qkv_forward(const void* act, int act_dtype, const void
     const DeviceWeight& w = W[i];
     // a weight that cannot reuse the shared fp16 copy (other K tile, act-order, int8 arithmetic) writes its own
     // conversion / u8 codes at the start of the same workspace: the copy is gone for the weights after it
-    const bool reuses = pp && !int8_compute(w) && pipelined_gemm(w, m) && !w.shuffle && pp->kp == w.nt * k_tile(w);
+    const bool reuses = pp && !int8_compute(w) && pipelined_gemm(w, m) && !w.shuffle && pp->kp == w.nt * tile_k(w.bits);
     const bool clobbers = !reuses && (int8_compute(w) || pipelined_gemm(w, m));
     if (run_gemm(x, w, Out{outs[i], ldos[i]}, Epi{}, st, reuses ? pp : nullptr)) return -1;
     if (clobbers && pp && pp->p != act) pp = nullptr;

@@ -5,7 +5,7 @@
 // (capi_internal.h: dry_run): every launch statement records itself instead of launching (planned), and the record is
 // written out.
 // The hot path is woq_gemv_m1_routed_kernel, or woq_gemv_routed_kernel for a general bank's int4 g32 / int8 weights
-// (woq_gemv.hip), or woq_q6k_gemv_routed_kernel for a bank of GGUF Q6_K experts (woq_q6k.hip); the bank's device table
+// (woq_gemv.h), or woq_q6k_gemv_routed_kernel for a bank of GGUF Q6_K experts (woq_q6k.hip); the bank's device table
 // is the feature's only allocation.  For prefill sizes the sorted, grouped entries (nad_device_moe_ffn_grouped,
 // nad_device_mul_mat_id_grouped): moe_sort_kernel (woq_moe.hip), then woq_gemm7_grouped_kernel (woq_gemm7.hip) -- a
 // Q6_K bank: woq_q6k_gemm_grouped_kernel -- over every expert's sorted rows.

@@ -1,4 +1,4 @@
-// woq_gemv_body.inc -- the body of the stripe-stream GEMV (woq_gemv.hip: steps 1-4 of woq_gemv_kernel), included once
+// woq_gemv_body.inc -- the body of the stripe-stream GEMV (woq_gemv.h: steps 1-4 of woq_gemv_kernel), included once
 // by each kernel that runs it, inside the kernel function, with
 //   GEMV_WG_INDEX, GEMV_WG_COUNT   this workgroup's index among the workgroups that share the launch's units, and how
 //                                  many they are (woq_gemv_kernel: blockIdx.x, gridDim.x; woq_gemv_routed_kernel: b % wpp,

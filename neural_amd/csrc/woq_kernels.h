@@ -112,7 +112,7 @@ struct GemvBatchEnt {
   const void* pad[3];  // 64 B per entry (one scalar-cache line)
 };
 
-// Persistent stripe-stream decode GEMV (woq_gemv.hip).  All weights of one launch share K, group size, scale type and
+// Persistent stripe-stream decode GEMV (woq_gemv.h).  All weights of one launch share K, group size, scale type and
 // symmetry; for the dual epilogues w[0] = gate, w[1] = up.
 struct GemvArgs {
   const void* A;
@@ -261,7 +261,7 @@ hipError_t launch_moe_gather(const MoeGatherArgs& a, hipStream_t stream);
 //   uqr    u_q | u_r << 16
 //   geom   nt | ng << 9 | tpg_shift << 20 | scale_t << 25 | waves << 27
 //   ns0    stripes of weight 0 (the pair: of both); the buffer-resource sizes follow from it
-// (m1s_packable() in woq_gemv.hip holds the field widths).  Everything else is the by-value GemvM1Rest that comes last
+// (m1s_packable() in woq_gemv_launch.h holds the field widths).  Everything else is the by-value GemvM1Rest that comes last
 // and is read by scalar loads behind the first loads, as before.  GemvM1Args is what the kernel puts the two together
 // into: the view its stream and tail work on, never a kernel argument itself.
 constexpr int kM1GeomNgShift = 9, kM1GeomTpgShift = 20, kM1GeomScaleShift = 25, kM1GeomWavesShift = 27;
@@ -450,13 +450,27 @@ int gemv_waves(int bits, int nt, int ng, int bs);
 // 4 = never)
 void gemv_lean_slices(GemvArgs& a, int bits, int* waves, int ks_pref);
 hipError_t launch_gemv(const GemvArgs& a, int bits, int waves, int grid, size_t lds, hipStream_t stream);
+// What launch_gemv, launch_gemv_batch and launch_gemv_routed hand on to, each defined in the object that holds the
+// instantiations it reaches (woq_gemv.o itself: woq_gemv_kernel, the int4 woq_gemv_m1_kernel, woq_gemv_m1_dual_kernel):
+//   woq_gemv_b2.o   the int2 woq_gemv_m1_kernel
+hipError_t gemv_m1_launch_b2(const GemvArgs& a, int gpt, dim3 g, dim3 b, size_t lds, hipStream_t st);
+//   woq_gemv_s2.o / _s3.o   the int4 / int2 woq_gemv_m1s_kernel.  false: no instantiation serves the launch, nothing
+//   was issued and e is untouched; true: the launch was issued (in a dry run: named), e is its status
+bool gemv_m1s_launch_b4(const GemvArgs& a, int gpt, dim3 g, dim3 b, size_t lds, hipStream_t st, hipError_t& e);
+bool gemv_m1s_launch_b2(const GemvArgs& a, int gpt, dim3 g, dim3 b, size_t lds, hipStream_t st, hipError_t& e);
+//   woq_gemv_s6.o   woq_gemv_m1s_kernel's load-ahead forms (form 1 / 2 / 3: m1s_ahead_form, woq_gemv_launch.h)
+hipError_t gemv_m1s_ahead_launch(const GemvArgs& a, int form, dim3 g, dim3 b, size_t lds, hipStream_t st);
+//   woq_gemv_r5.o   the int2 woq_gemv_m1_routed_kernel (woq_gemv_r4.o: launch_gemv_routed with the int4 ones;
+//   woq_gemv_r7.o: launch_gemv_routed_general with woq_gemv_routed_kernel)
+hipError_t gemv_routed_launch_b2(const GemvArgs& a, const GemvRouted& r, int gpt, dim3 g, dim3 b, size_t lds,
+                                 hipStream_t st);
 // Dry runs (nad_plan_*): between gemv_name_begin() and gemv_name_end() on the calling thread launch_gemv and
 // launch_gemv_batch run as always up to the launch itself, which records its kernel's template arguments instead of
 // being issued -- the name comes from the statement that would have launched.  gemv_name_end() returns the record of the
 // last such launch (gemv_inst below), 0 if there was none.
 void gemv_name_begin();
 uint32_t gemv_name_end();
-bool gemv_named(uint32_t inst);  // woq_gemv.hip's launch statements: true (and inst recorded) while naming
+bool gemv_named(uint32_t inst);  // the launch statements of woq_gemv_launch.h: true (and inst recorded) while naming
 // family 1 woq_gemv_kernel (at = HILO; ksn, spw, st, nwt, nsc: 0 / -1), 2 woq_gemv_m1_kernel, 3 woq_gemv_m1s_kernel;
 // bits, gpt in {1, 2, 4, 8}; st -1..2; nsc in {0, 7, 11, 16}
 constexpr uint32_t gemv_inst(int family, int bits, int gpt, bool asym, int at, int ksn, int spw, int nst, int st,
@@ -470,10 +484,6 @@ constexpr uint32_t gemv_inst(int family, int bits, int gpt, bool asym, int at, i
 constexpr int kPlanGemvInstShift = 4;  // the record's place in the plan's flag word (o[4] of nad_plan_*)
 // whether launch_gemv would take woq_gemv_m1_kernel for these arguments
 bool gemv_uses_m1(const GemvArgs& a, int bits, int waves);
-// ... and would serve it with woq_gemv_m1s_kernel (a.m1_spec, and an instantiation for the launch exists)
-bool gemv_uses_m1s(const GemvArgs& a, int bits, int waves);
-// ... in its load-ahead order (a.m1_spec & kM1SpecAhead, and a form exists for the launch)
-bool gemv_uses_ahead(const GemvArgs& a, int bits, int waves);
 // two M = 1 launches of different formats as one (int2 a + int4 b at groups of 64 or 128, fp32 activations, sym,
 // 16 waves each; a on workgroups [0, ga), b on [ga, ga + gb))
 bool gemv_dual_ok(const GemvArgs& a, int bits_a, const GemvArgs& b, int bits_b, int waves);

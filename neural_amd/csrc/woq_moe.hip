@@ -1,4 +1,4 @@
-// woq_moe.hip -- the two small kernels around the routed expert matmuls (woq_gemv_m1_routed_kernel, woq_gemv.hip) of a
+// woq_moe.hip -- the two small kernels around the routed expert matmuls (woq_gemv_m1_routed_kernel, woq_gemv.h) of a
 // Mixtral-style FFN (models/llama/llama.cpp:620-688): the router (softmax -> top_k -> renormalise, :624-638) and the
 // weighted sum of the slot results (ne_mul then ne_add per slot, :676-679); and around the sorted, grouped form
 // (woq_gemm7_grouped_kernel, woq_gemm7.hip): the sort of the problems by expert and the same sum over sorted rows.

@@ -1,6 +1,6 @@
 """The decode GEMV instantiations compiled into the library are exactly the ones accounted for (no GPU needed).
 
-woq_gemv.hip compiles five kernel templates.  Every function symbol of theirs in the built library's gfx950 code objects
+woq_gemv.h holds five kernel templates.  Every function symbol of theirs in the built library's gfx950 code objects
 must be in one of three literal sets, and every member of the sets must be compiled:
 
   TABLE      what tests/test_gemv_matrix_gpu.py runs by name: woq_gemv_kernel, woq_gemv_m1_kernel, woq_gemv_m1s_kernel;

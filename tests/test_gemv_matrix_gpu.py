@@ -1,6 +1,6 @@
 """Every reachable decode GEMV instantiation, run by name against the exact hi / lo model (tests/mid_model.py).
 
-woq_gemv.hip compiles woq_gemv_kernel, woq_gemv_m1_kernel and woq_gemv_m1s_kernel 1169 times over bits x groups per K
+woq_gemv.h is compiled into woq_gemv_kernel, woq_gemv_m1_kernel and woq_gemv_m1s_kernel 1169 times over bits x groups per K
 tile x sym / asym x activation type x K-slice width and slices per wave x register stages x scale type x weight count
 x reduce form x load-ahead order.  The dry run names the instantiation its launch statement selects (plan["instance"]);
 here every launch first holds that name to a literal table -- transcribed from gemv_waves, gemv_lean_slices, lean_ok,

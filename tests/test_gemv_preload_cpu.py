@@ -28,7 +28,7 @@ def rows():
     tool = _tool()
     if tool.hipcc_path() is None or tool.find_tool("llvm-objdump") is None or tool.find_tool("llvm-readelf") is None:
         pytest.skip("hipcc / llvm-objdump / llvm-readelf not found")
-    src = os.path.join(REPO, "neural_amd", "csrc", "woq_gemv.hip")
+    src = os.path.join(REPO, "neural_amd", "csrc", "woq_gemv.h")
     return {label: (tid, f) for label, tid, f in tool.report(src, tool.kernel_sets(False)["all"])}
 
 

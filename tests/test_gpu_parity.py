@@ -402,7 +402,7 @@ def test_qkv_mixed_formats(oracle, m, kinds):
 @pytest.mark.parametrize("cfg", [(1024, 4096, 64, False, "f32"), (528, 2048, 128, True, "f16"),
                                  (300, 1024, 256, False, "bf16"), (4096, 4096, 64, False, "f16")])
 def test_gemv_m1_int2_every_scale_type(oracle, st, cfg):
-    """Round 6: the int2 M = 1 instantiations take the scale type as a template parameter (woq_gemv.hip
+    """Round 6: the int2 M = 1 instantiations take the scale type as a template parameter (woq_gemv_launch.h
     gemv_m1_launch4, compiled as woq_gemv_b2.o).  Every scale type x group layout (4 / 2 / 1 groups per 256-deep tile)
     against the oracle, and the batched form of the same kernel bit-identical to single launches."""
     n, k, bs, asym, adt = cfg

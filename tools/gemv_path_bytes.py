@@ -3,7 +3,7 @@
 
 A decode launch pays for the code it executes where no memory latency hides it (the instruction cache starts cold on
 every dispatch): everything before the first weight-tile load, and everything after the barrier.  This tool
-cross-compiles csrc/woq_gemv.hip for gfx950 (device code only, just the named instantiations, no launchers), disassembles
+cross-compiles csrc/woq_gemv.h for gfx950 (device code only, just the named instantiations, no launchers), disassembles
 the object and prints, per kernel:
 
   preload          dwords of leading kernel arguments the hardware delivers in SGPRs at dispatch (the kernel
@@ -73,7 +73,7 @@ def kernel_sets(legacy):
                 ("generic down", generic(4, 1, "f32", False, 4, 2, False, 1))]
     rest += [("asym/bf16-scale (generic)", generic(4, 1, "f32", True, 2, 1, False, 1)),
              ("batched", generic(4, 1, "f32", False, 2, 1, True, 3))]
-    # the load-ahead forms (GEMV_PART=6), each behind the present form of the same launch
+    # the load-ahead forms (woq_gemv_s6.hip), each behind the present form of the same launch
     ahead = []
     if not legacy:
         for label, asym, ksn, spw, nwt, nsc in (("qkv (3 weights)", False, 2, 1, 3, 16), ("gate/up (pair)", False, 2, 1, 2, 16),
@@ -99,7 +99,12 @@ def hipcc_path():
 
 
 def compile_kernels(source, kernels, workdir, arch="gfx950"):
-    """Device-only object holding exactly `kernels` [(template-id, arg type)]; returns its path."""
+    """Device-only object holding exactly `kernels` [(template-id, arg type)]; returns its path.  `source` may be a
+    tree's woq_gemv.hip in either layout: where woq_gemv.h lies beside it, the kernels are there and the .hip holds
+    launchers that would instantiate an object's worth of them."""
+    header = os.path.splitext(source)[0] + ".h"
+    if source.endswith(".hip") and os.path.exists(header):
+        source = header
     wrap = os.path.join(workdir, "gemv_only.hip")
     with open(wrap, "w") as f:
         f.write('#include "%s"\nnamespace nad {\n' % os.path.abspath(source))
@@ -107,7 +112,8 @@ def compile_kernels(source, kernels, workdir, arch="gfx950"):
             f.write("template __global__ void %s(%s);\n" % (tid, arg))
         f.write("}\n")
     obj = os.path.join(workdir, "gemv_only.o")
-    # GEMV_PART=99: no launcher section (they would instantiate every kernel of the object)
+    # GEMV_PART=99: for an older tree's woq_gemv.hip, whose launcher section (it would instantiate every kernel of
+    # the object) that value leaves out; csrc/woq_gemv.h holds no launchers and does not read it
     # the preload flag of the Makefile's GEMV_PRELOAD (kernels whose first parameter is a struct keep length 0)
     cmd = [hipcc_path(), "--offload-arch=" + arch, "--cuda-device-only", "--no-gpu-bundle-output", "-O3", "-std=c++17",
            "-mllvm", "-amdgpu-kernarg-preload-count=14", "-DGEMV_PART=99", "-I", os.path.dirname(os.path.abspath(source)), "-Wno-unused-function", "-c", wrap, "-o", obj]
@@ -305,7 +311,7 @@ COLS = ["preload", "pro_ins", "pro_B", "lgkm", "vm", "tail_B", "barriers", "tota
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--source", default=os.path.join(ROOT, "neural_amd", "csrc", "woq_gemv.hip"))
+    ap.add_argument("--source", default=os.path.join(ROOT, "neural_amd", "csrc", "woq_gemv.h"))
     ap.add_argument("--set", default="all", choices=["all", "headline", "ahead"])
     ap.add_argument("--legacy", action="store_true", help="the source has no woq_gemv_m1s_kernel: list the generic ones")
     ap.add_argument("--keep", default=None, help="directory to keep the wrapper source and the object in")
