@@ -524,6 +524,44 @@ int nad_device_moe_ffn(const void* gate_bank, const void* up_bank, const void* d
  * (ne_layers.c): weights agree with it to fp16 table precision only, and near-ties may order differently. */
 int nad_moe_route(const float* logits, int ld, int m, int n_expert, int top_k, int32_t* ids, int ids_ld, float* wts,
                   int wts_ld, void* queue);
+/* The router from the hidden state: logits = the ffn_gate_inp matmul (llama.cpp:631, grok.cpp:292) of an UNQUANTIZED
+ * gate, then nad_moe_route's arithmetic on them, in ONE launch (moe_gate_route_kernel: one workgroup of 1024 threads
+ * per row, no workspace, no atomics, nothing between workgroups).  Nothing is copied to the host, synchronised or
+ * allocated: graph-capturable, and a replay follows act and gate as they are rewritten on the device.
+ *   act    device memory, fp32 [m][lda]
+ *   gate   device memory, [n_expert][ldw] of gate_dtype: NAD_ACT_F32, NAD_ACT_F16 or NAD_ACT_BF16 (what
+ *          convert_quantized_mixtral.py and GGUF files keep ffn_gate_inp.weight as)
+ * Arithmetic, part of the ABI like nad_moe_route's.  For row r and expert e let x = act[r] and w = gate[e], an fp16 or
+ * bf16 w widened exactly to fp32.  Every product and every sum below is an fp32 operation rounded on its own (no fused
+ * multiply-add):
+ *   slots   1024 slots t, each starting at +0.0f.  For pass i = 0, 1, ... and j = 0..3 in that order slot t adds
+ *           x[k] * w[k] with k = 4 (t + 1024 i) + j; elements with k >= K are skipped (the same as adding +0.0f: a sum
+ *           that starts at +0.0f never becomes -0.0f).
+ *   waves   the 64 slots of wave t >> 6 are summed by the xor butterfly s = s + shfl_xor(s, o), o = 32, 16, ..., 1
+ *           (addition commutes, so every lane ends with the same value).
+ *   row     the 16 waves' sums are added in wave order: logit = ((s0 + s1) + s2) + ... + s15.
+ *   route   ids and wts are nad_moe_route's function of these logits (the same device code computes them).
+ * The result for a row depends on that row, the gate and K alone: not on m, the row's index, n_expert, the grid, or the
+ * gate's storage type (an fp16 gate gives the bits of its fp32 widening).  A token is routed the same alone and inside
+ * a prompt.  numpy float32 reproduces the logits bit for bit (tests/gate_model.py); against the exact dot product
+ * they lie within depth * 2^-24 * sum |x_k w_k|, depth = 4 * passes + 6 + 15 + 1, passes = ceil(K / 4096).
+ * Non-finite logits are as undefined as in nad_moe_route.
+ * Windows: writes exactly ids[0:m, 0:top_k] and wts[0:m, 0:top_k], and logits[0:m, 0:n_expert] when logits is not
+ * NULL; reads act and gate only inside [.., 0:k].
+ * Refused with -1 before any launch, nad_last_error() naming the argument: a null act, gate, ids or wts; m < 0; k < 4
+ * or k % 4 != 0; n_expert outside 1..64; top_k outside 1..n_expert; an unknown gate_dtype; lda or ldw below k or not a
+ * multiple of 4; ids_ld or wts_ld below top_k; logits_ld below n_expert when logits is given; act or gate not 16-byte
+ * aligned.  m == 0 returns 0 and launches nothing.
+ * Not for a gate that the reference's quantizer turned into a BTLA blob (nad_device_forward + nad_moe_route serve
+ * that), and not the reference's ne_soft_max (see nad_moe_route). */
+#define NAD_KERNEL_MOE_GATE_ROUTE 24 /* moe_gate_route_kernel: the gate matmul and the router of one row per workgroup */
+int nad_moe_gate_route(const float* act, int lda, const void* gate, int gate_dtype, int ldw, int m, int k, int n_expert,
+                       int top_k, int32_t* ids, int ids_ld, float* wts, int wts_ld, float* logits, int logits_ld,
+                       void* queue);
+/* Dry run of nad_moe_gate_route (no launch, no GPU needed), m >= 1: [NAD_KERNEL_MOE_GATE_ROUTE, grid = m, 1024, dynamic
+ * LDS bytes = 16 * n_expert * 4, the launch count 1].  Writes min(nout, 5), returns the number written or -1 (the
+ * entry's own refusals, by the same texts). */
+int nad_plan_moe_gate_route(int m, int k, int n_expert, int top_k, int gate_dtype, int64_t* out, int nout);
 /* Dry run of nad_device_moe_ffn (no launch, no GPU needed; geometry-only banks qualify): per launch [kernel
  * NAD_KERNEL_*, grid, threads per workgroup, dynamic LDS bytes] -- 1 gate + up, 2 down (each NAD_KERNEL_GEMV_ROUTED, or
  * NAD_KERNEL_GEMV_ROUTED_GENERAL for a bank of route kind 1, NAD_KERNEL_Q6K_GEMV_ROUTED for kind 2; grid = m * top_k *

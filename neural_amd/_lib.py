@@ -123,6 +123,8 @@ SIGNATURES = {
     "nad_moe_workspace_size": (_sz, [_i, _i, _i, _i]),
     "nad_device_moe_ffn": (_i, [_p, _p, _p, _p, _p, _i, _p, _i, _i, _i, _p, _p, _i, _i, _i, _p]),
     "nad_moe_route": (_i, [_p, _i, _i, _i, _i, _p, _i, _p, _i, _p]),
+    "nad_moe_gate_route": (_i, [_p, _i, _p, _i, _i, _i, _i, _i, _i, _p, _i, _p, _i, _p, _i, _p]),
+    "nad_plan_moe_gate_route": (_i, [_i, _i, _i, _i, _i, _p, _i]),
     "nad_plan_moe": (_i, [_p, _p, _p, _i, _i, _p, _i]),
     "nad_moe_grouped_workspace_size": (_sz, [_p, _p, _p, _i, _i]),
     "nad_device_moe_ffn_grouped": (_i, [_p, _p, _p, _p, _p, _i, _p, _i, _i, _i, _p, _p, _i, _i, _i, _p]),

@@ -13,7 +13,7 @@ Reference entry points mirrored (paths relative to the reference repo root):
                     <- ne_get_rows on a quantized tensor (ne_compute_forward_get_rows_q, core/ne_layers.c:8385-8433)
   qkv_forward()     <- bestla_fusion_QKV_f32f32_forward (ip_fusion_qkv.cpp)
   ffn_forward()     <- bestla_fusion_FFN_SiLu_f32f32_forward / _Gelu_Mul_ (ip_fusion_ffn.cpp:734-755)
-  ExpertBank / mul_mat_id() / moe_ffn() / moe_route()
+  ExpertBank / mul_mat_id() / moe_ffn() / moe_route() / moe_gate_route()
                     <- ne_mul_mat_id / ne_mul_id_ffn_silu and the router of models/llama/llama.cpp:620-688
   split()           <- TP weight split of model_files.h:1538-1660 (here exact: no re-quantization)
 
@@ -183,7 +183,7 @@ KERNELS = {1: "woq_gemv_m1_kernel", 2: "woq_gemv_kernel", 3: "woq_skinny_kernel"
            13: "woq_q6k_i8_kernel", 14: "woq_gemv_m1_routed_kernel", 15: "moe_combine_kernel", 16: "moe_sort_kernel",
            17: "nad_cvt_act_kernel", 18: "woq_gemm7_grouped_kernel", 19: "moe_gather_kernel",
            20: "woq_get_rows_kernel", 21: "woq_gemv_routed_kernel", 22: "woq_q6k_gemv_routed_kernel",
-           23: "woq_q6k_gemm_grouped_kernel"}
+           23: "woq_q6k_gemm_grouped_kernel", 24: "moe_gate_route_kernel"}
 
 
 _SCALE_CODE = {"fp32": 0, "bf16": 1, "fp16": 2}  # ScaleType (woq_layout.h)
@@ -785,6 +785,37 @@ def moe_route(logits, top_k, stream=None):
     check(lib().nad_moe_route(_ptr(logits), logits.stride(0), m, ne, top_k, _ptr(ids), top_k, _ptr(wts), top_k,
                               _stream(stream)), "nad_moe_route")
     return ids, wts
+
+
+def moe_gate_route(x, gate, top_k, *, return_logits=False, stream=None):
+    """The router from the hidden state in one launch (nad_moe_gate_route): logits = x . gate^T in the order the header
+    defines -- a function of the row, the gate and K alone, whatever M -- then moe_route's arithmetic on them.  x cuda
+    fp32 [M][K]; gate cuda [n_expert <= 64][K], float32, float16 or bfloat16 (the unquantized ffn_gate_inp.weight); row
+    strides honoured (multiples of 4, 16-byte aligned bases) -> (ids int32 [M][top_k], wts fp32 [M][top_k]), and the
+    logits fp32 [M][n_expert] with return_logits."""
+    torch = _torch()
+    m, k = x.shape
+    ne, kw = gate.shape
+    if x.dtype != torch.float32 or kw != k or x.stride(1) != 1 or gate.stride(1) != 1:
+        raise TypeError(f"moe_gate_route: x must be float32 [M][K] and gate [n_expert][K], rows contiguous "
+                        f"(x {x.dtype} {tuple(x.shape)}, gate {tuple(gate.shape)})")
+    ids = torch.empty((m, top_k), dtype=torch.int32, device=x.device)
+    wts = torch.empty((m, top_k), dtype=torch.float32, device=x.device)
+    logits = torch.empty((m, ne), dtype=torch.float32, device=x.device) if return_logits else None
+    check(lib().nad_moe_gate_route(_ptr(x), x.stride(0), _ptr(gate), _act_code(gate), gate.stride(0), m, k, ne, top_k,
+                                   _ptr(ids), top_k, _ptr(wts), top_k, _ptr(logits), ne, _stream(stream)),
+          "nad_moe_gate_route")
+    return (ids, wts, logits) if return_logits else (ids, wts)
+
+
+def plan_moe_gate_route(m, k, n_expert, top_k, gate_dtype="fp32"):
+    """What moe_gate_route launches for m rows (nad_plan_moe_gate_route: no launch, no GPU needed):
+    dict(kernel, grid, threads, lds, launches)."""
+    o = np.zeros(5, np.int64)
+    if lib().nad_plan_moe_gate_route(m, k, n_expert, top_k, _ACT_CODE[gate_dtype], _ptr(o), 5) != 5:
+        raise RuntimeError(f"nad_plan_moe_gate_route failed: {last_error()}")
+    return dict(kernel=KERNELS.get(int(o[0]), str(int(o[0]))), grid=int(o[1]), threads=int(o[2]), lds=int(o[3]),
+                launches=int(o[4]))
 
 
 def plan_moe(gate, up, down, m, top_k):

@@ -1,6 +1,7 @@
 // capi_moe.hip -- Mixtral-style expert FFNs with the routing read on the device (include/neural_amd.h, "routed expert
 // matmuls"): the expert bank, nad_device_mul_mat_id (ne_mul_mat_id, ne_layers.c:2384-2462, 7783-7916),
-// nad_device_moe_ffn (models/llama/llama.cpp:641-679), the router (llama.cpp:624-638) and the dry runs.  A dry run
+// nad_device_moe_ffn (models/llama/llama.cpp:641-679), the router (llama.cpp:624-638), alone (nad_moe_route) or behind
+// the unquantized gate's matmul in the same launch (nad_moe_gate_route, llama.cpp:631), and the dry runs.  A dry run
 // (nad_plan_moe, nad_plan_moe_grouped) is the entry's own body run on stand-in arguments under the launch recorder
 // (capi_internal.h: dry_run): every launch statement records itself instead of launching (planned), and the record is
 // written out.
@@ -810,4 +811,65 @@ extern "C" int nad_moe_route(const float* logits, int ld, int m, int n_expert, i
   return launch(planned_pass(), "moe route kernel", [&] { return launch_moe_route(a, static_cast<hipStream_t>(queue)); })
              ? 0
              : -1;
+}
+
+// ------------------------------------------------------------------------------------------------ gate matmul + route
+namespace {
+// nad_moe_gate_route's refusals, each naming its argument, then the one launch (recorded in a dry run)
+int moe_gate_route(const MoeGateRouteArgs& a, hipStream_t st, const char* who) {
+  const auto misaligned = [](const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 != 0; };
+  if (!a.act || !a.gate || !a.ids || !a.wts)
+    set_err("%s: %s is null", who, !a.act ? "act" : !a.gate ? "gate" : !a.ids ? "ids" : "wts");
+  else if (a.m < 0)
+    set_err("%s: m (%d) is negative", who, a.m);
+  else if (a.k < 4 || a.k % 4 != 0)
+    set_err("%s: k (%d) must be a multiple of 4, at least 4", who, a.k);
+  else if (a.n_expert < 1 || a.n_expert > 64)
+    set_err("%s: n_expert (%d) is outside 1..64", who, a.n_expert);
+  else if (a.top_k < 1 || a.top_k > a.n_expert)
+    set_err("%s: top_k (%d) is outside 1..n_expert (%d)", who, a.top_k, a.n_expert);
+  else if (a.gate_t != kActF32 && a.gate_t != kActF16 && a.gate_t != kActBF16)
+    set_err("%s: gate_dtype (%d) is none of NAD_ACT_F32, NAD_ACT_F16, NAD_ACT_BF16", who, a.gate_t);
+  else if (a.lda < a.k || a.lda % 4 != 0)
+    set_err("%s: lda (%d) must be a multiple of 4, at least k (%d)", who, a.lda, a.k);
+  else if (a.ldw < a.k || a.ldw % 4 != 0)
+    set_err("%s: ldw (%d) must be a multiple of 4, at least k (%d)", who, a.ldw, a.k);
+  else if (a.ids_ld < a.top_k)
+    set_err("%s: ids_ld (%d) is below top_k (%d)", who, a.ids_ld, a.top_k);
+  else if (a.wts_ld < a.top_k)
+    set_err("%s: wts_ld (%d) is below top_k (%d)", who, a.wts_ld, a.top_k);
+  else if (a.logits && a.logits_ld < a.n_expert)
+    set_err("%s: logits_ld (%d) is below n_expert (%d)", who, a.logits_ld, a.n_expert);
+  else if (misaligned(a.act) || misaligned(a.gate))
+    set_err("%s: %s is not 16-byte aligned", who, misaligned(a.act) ? "act" : "gate");
+  else if (a.m == 0)
+    return 0;
+  else
+    return launch(planned(NAD_KERNEL_MOE_GATE_ROUTE, moe_gate_route_shape(a.m), moe_gate_route_lds(a.n_expert)),
+                  "moe gate route kernel", [&] { return launch_moe_gate_route(a, st); })
+               ? 0
+               : -1;
+  return -1;
+}
+}  // namespace
+
+extern "C" int nad_moe_gate_route(const float* act, int lda, const void* gate, int gate_dtype, int ldw, int m, int k,
+                                  int n_expert, int top_k, int32_t* ids, int ids_ld, float* wts, int wts_ld,
+                                  float* logits, int logits_ld, void* queue) {
+  return moe_gate_route(MoeGateRouteArgs{act, lda, gate, gate_dtype, ldw, m, k, n_expert, top_k, ids, ids_ld, wts,
+                                         wts_ld, logits, logits_ld},
+                        static_cast<hipStream_t>(queue), "nad_moe_gate_route");
+}
+
+extern "C" int nad_plan_moe_gate_route(int m, int k, int n_expert, int top_k, int gate_dtype, int64_t* out, int nout) {
+  const char* who = "nad_plan_moe_gate_route";
+  if (!out || nout < 0 || m <= 0) {
+    set_err("%s: bad arguments (m=%d: a dry run needs m >= 1)", who, m);
+    return -1;
+  }
+  // stand-ins: contiguous rows of k, no logits output (it changes nothing about the launch)
+  const MoeGateRouteArgs a{stand_in<const float>(kStandAct), k, stand_in<const void>(kStandWeight), gate_dtype, k, m, k,
+                           n_expert, top_k, stand_in<int32_t>(kStandMoeIds), top_k, stand_in<float>(kStandMoeWts), top_k,
+                           nullptr, 0};
+  return dry_run_list(out, nout, nullptr, 0, [&] { return moe_gate_route(a, nullptr, who); });
 }

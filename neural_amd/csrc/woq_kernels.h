@@ -206,6 +206,27 @@ struct MoeRouteArgs {
   int wts_ld;
 };
 hipError_t launch_moe_route(const MoeRouteArgs& a, hipStream_t stream);
+// The gate matmul and the router in one launch (nad_moe_gate_route): logits[r][e] = act[r] . gate[e] in the order the
+// header defines, then MoeRouteArgs' arithmetic on them.  One workgroup of 1024 threads per row, dynamic LDS
+// [16][n_expert] floats.  k % 4 == 0, lda % 4 == 0, ldw % 4 == 0, act and gate 16-byte aligned (the entry checks).
+struct MoeGateRouteArgs {
+  const float* act;  // [m][lda]
+  int lda;
+  const void* gate;  // [n_expert][ldw] of gate_t (ActType)
+  int gate_t, ldw;
+  int m, k, n_expert, top_k;
+  int32_t* ids;
+  int ids_ld;
+  float* wts;
+  int wts_ld;
+  float* logits;  // [m][logits_ld], or null
+  int logits_ld;
+};
+#pragma GCC visibility push(hidden)
+LaunchShape moe_gate_route_shape(int m);
+size_t moe_gate_route_lds(int n_expert);
+#pragma GCC visibility pop
+hipError_t launch_moe_gate_route(const MoeGateRouteArgs& a, hipStream_t stream);
 
 // Sorted, grouped expert GEMMs (nad_device_moe_ffn_grouped / nad_device_mul_mat_id_grouped).  Problem p = r * top_k + i
 // has expert ids[r * ids_ld + i] and is valid when that lies in [0, n_expert).  moe_sort_kernel, one workgroup, writes

@@ -1,7 +1,8 @@
-// woq_moe.hip -- the two small kernels around the routed expert matmuls (woq_gemv_m1_routed_kernel, woq_gemv.h) of a
-// Mixtral-style FFN (models/llama/llama.cpp:620-688): the router (softmax -> top_k -> renormalise, :624-638) and the
-// weighted sum of the slot results (ne_mul then ne_add per slot, :676-679); and around the sorted, grouped form
-// (woq_gemm7_grouped_kernel, woq_gemm7.hip): the sort of the problems by expert and the same sum over sorted rows.
+// woq_moe.hip -- the small kernels around the routed expert matmuls (woq_gemv_m1_routed_kernel, woq_gemv.h) of a
+// Mixtral-style FFN (models/llama/llama.cpp:620-688): the router (softmax -> top_k -> renormalise, :624-638), alone or
+// behind the ffn_gate_inp matmul of an unquantized gate in the same launch (:631), and the weighted sum of the slot
+// results (ne_mul then ne_add per slot, :676-679); and around the sorted, grouped form (woq_gemm7_grouped_kernel,
+// woq_gemm7.hip): the sort of the problems by expert and the same sum over sorted rows.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -36,14 +37,14 @@ hipError_t launch_moe_combine(const MoeCombineArgs& a, hipStream_t stream) {
   return hipGetLastError();
 }
 
-// One wave per row; lane l holds expert l (n_expert <= 64).  All in fp32:
+// The router of one row on one wave; lane l holds expert l's logit x (n_expert <= 64; a lane past n_expert: -inf).
+// All in fp32:
 //   p = exp(x - max x) / sum exp(x - max x)      (the sum over the lanes as a butterfly: the same value in every lane)
 //   top_k rounds of arg max over the experts not yet taken, a tie going to the lower index
 //   wts[i] = p[ids[i]] / (p[ids[0]] + p[ids[1]] + ...), the sum added in slot order
-__global__ __launch_bounds__(64) void moe_route_kernel(MoeRouteArgs a) {
-  const int r = int(blockIdx.x), lane = int(threadIdx.x);
-  const bool live = lane < a.n_expert;
-  const float x = live ? a.logits[size_t(r) * a.ld + lane] : -INFINITY;
+// ids and wts are the row's own.  moe_route_kernel and moe_gate_route_kernel both route through it.
+__device__ __forceinline__ void moe_route_wave(float x, int lane, int n_expert, int top_k, int32_t* ids, float* wts) {
+  const bool live = lane < n_expert;
   float mx = x;
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
@@ -54,7 +55,7 @@ __global__ __launch_bounds__(64) void moe_route_kernel(MoeRouteArgs a) {
   const float p = e / sum;
   float v = live ? p : -1.f;  // -1: not a candidate (a lane past n_expert, or an expert already taken)
   float mine = 0.f, tot = 0.f;  // lane i < top_k: p of slot i; the slots' sum
-  for (int i = 0; i < a.top_k; i++) {
+  for (int i = 0; i < top_k; i++) {
     float bv = v;
     int bi = lane;
 #pragma unroll
@@ -71,14 +72,143 @@ __global__ __launch_bounds__(64) void moe_route_kernel(MoeRouteArgs a) {
     if (lane == bi) v = -1.f;
     if (lane == i) mine = ps;
     tot = i == 0 ? ps : tot + ps;
-    if (lane == 0) a.ids[size_t(r) * a.ids_ld + i] = bi;
+    if (lane == 0) ids[i] = bi;
   }
-  if (lane < a.top_k) a.wts[size_t(r) * a.wts_ld + lane] = mine / tot;
+  if (lane < top_k) wts[lane] = mine / tot;
+}
+
+// One wave per row (nad_moe_route)
+__global__ __launch_bounds__(64) void moe_route_kernel(MoeRouteArgs a) {
+  const int r = int(blockIdx.x), lane = int(threadIdx.x);
+  const float x = lane < a.n_expert ? a.logits[size_t(r) * a.ld + lane] : -INFINITY;
+  moe_route_wave(x, lane, a.n_expert, a.top_k, a.ids + size_t(r) * a.ids_ld, a.wts + size_t(r) * a.wts_ld);
 }
 
 hipError_t launch_moe_route(const MoeRouteArgs& a, hipStream_t stream) {
   hipLaunchKernelGGL(moe_route_kernel, dim3(a.m), dim3(64), 0, stream, a);
   return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------ gate matmul + route
+// logits[r][e] = act[r] . gate[e] and the router on them, one workgroup of 16 waves per row (MoeGateRouteArgs,
+// woq_kernels.h; the order of the sums is the contract of nad_moe_gate_route, include/neural_amd.h):
+//   1. thread t is slot t: per pass of 4096 elements one 16-byte load of x at k = 4 (t + 1024 pass), and per expert one
+//      16-byte (fp32) or 8-byte (fp16, bf16) load of the gate at the same k.  The loads of kGateBatch experts are issued
+//      before their multiply-adds; acc[e] carries across the passes.  K % 4 == 0, so a slot's four elements are all
+//      inside K or all outside.
+//   2. per expert the xor butterfly over the wave; lane e keeps expert e's sum and writes it to part[wave][e] (LDS).
+//   3. after the one barrier lane e of wave 0 adds the 16 partials in wave order: logit e, the lane layout
+//      moe_route_wave starts from.
+// NEB bounds n_expert at compile time: acc[] is indexed by unrolled constants only and stays in registers.
+constexpr int kGateWaves = 16, kGateSlots = kGateWaves * 64, kGateBatch = 8;
+
+template <class W>
+struct GateLoad;
+template <>
+struct GateLoad<float> {
+  using Raw = float4;
+  static __device__ __forceinline__ float4 widen(const float4& v) { return v; }
+};
+template <>
+struct GateLoad<_Float16> {
+  using Raw = uint2;  // four fp16
+  static __device__ __forceinline__ float4 widen(const uint2& v) {
+    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+    const h2 a = __builtin_bit_cast(h2, v.x), b = __builtin_bit_cast(h2, v.y);
+    return make_float4(float(a.x), float(a.y), float(b.x), float(b.y));
+  }
+};
+struct GateBf16 {};
+template <>
+struct GateLoad<GateBf16> {
+  using Raw = uint2;  // four bf16: the upper halves of their fp32 values
+  static __device__ __forceinline__ float4 widen(const uint2& v) {
+    return make_float4(__uint_as_float(v.x << 16), __uint_as_float(v.x & 0xffff0000u), __uint_as_float(v.y << 16),
+                       __uint_as_float(v.y & 0xffff0000u));
+  }
+};
+
+template <int NEB, class W>
+__global__ __launch_bounds__(kGateSlots) void moe_gate_route_kernel(MoeGateRouteArgs a) {
+  using Raw = typename GateLoad<W>::Raw;
+  extern __shared__ float gate_part[];  // [kGateWaves][n_expert]
+  const int r = int(blockIdx.x), t = int(threadIdx.x), lane = t & 63, wave = t >> 6;
+  const int ne = a.n_expert;
+  const float* x = a.act + size_t(r) * a.lda;
+  const Raw* g = static_cast<const Raw*>(a.gate);  // a Raw holds four elements; ldw % 4 == 0
+  const size_t ldw4 = size_t(a.ldw >> 2);
+  float acc[NEB];
+#pragma unroll
+  for (int e = 0; e < NEB; e++) acc[e] = 0.0f;
+  for (int k = 4 * t; k < a.k; k += 4 * kGateSlots) {
+    const float4 xv = *reinterpret_cast<const float4*>(x + k);
+    const Raw* gk = g + (k >> 2);
+#pragma unroll
+    for (int e0 = 0; e0 < NEB; e0 += kGateBatch) {
+      if (e0 >= ne) continue;  // uniform; no break: the loops unroll fully, so acc[] is indexed by constants
+      Raw raw[kGateBatch];
+#pragma unroll
+      for (int j = 0; j < kGateBatch; j++)
+        if (e0 + j < ne) raw[j] = gk[size_t(e0 + j) * ldw4];
+#pragma unroll
+      for (int j = 0; j < kGateBatch; j++)
+        if (e0 + j < ne) {
+          const float4 w = GateLoad<W>::widen(raw[j]);
+          float s = acc[e0 + j];
+          s = s + xv.x * w.x;
+          s = s + xv.y * w.y;
+          s = s + xv.z * w.z;
+          s = s + xv.w * w.w;
+          acc[e0 + j] = s;
+        }
+    }
+  }
+  float mine = 0.0f;  // lane e: the wave's sum of expert e
+#pragma unroll
+  for (int e = 0; e < NEB; e++) {
+    if (e >= ne) continue;
+    float s = acc[e];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s = s + __shfl_xor(s, o, 64);
+    if (lane == e) mine = s;
+  }
+  if (lane < ne) gate_part[wave * ne + lane] = mine;
+  __syncthreads();
+  if (wave != 0) return;
+  float logit = -INFINITY;
+  if (lane < ne) {
+    logit = gate_part[lane];
+    for (int w = 1; w < kGateWaves; w++) logit = logit + gate_part[w * ne + lane];
+    if (a.logits) a.logits[size_t(r) * a.logits_ld + lane] = logit;
+  }
+  moe_route_wave(logit, lane, ne, a.top_k, a.ids + size_t(r) * a.ids_ld, a.wts + size_t(r) * a.wts_ld);
+}
+
+LaunchShape moe_gate_route_shape(int m) { return {m, kGateSlots}; }
+size_t moe_gate_route_lds(int n_expert) { return size_t(kGateWaves) * size_t(n_expert) * sizeof(float); }
+
+template <class W>
+static hipError_t launch_gate_route_as(const MoeGateRouteArgs& a, hipStream_t stream) {
+  const LaunchShape s = moe_gate_route_shape(a.m);
+  const size_t lds = moe_gate_route_lds(a.n_expert);
+  const dim3 grid(unsigned(s.grid)), block(s.block);
+  if (a.n_expert <= 8)
+    hipLaunchKernelGGL((moe_gate_route_kernel<8, W>), grid, block, lds, stream, a);
+  else if (a.n_expert <= 16)
+    hipLaunchKernelGGL((moe_gate_route_kernel<16, W>), grid, block, lds, stream, a);
+  else
+    hipLaunchKernelGGL((moe_gate_route_kernel<64, W>), grid, block, lds, stream, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_moe_gate_route(const MoeGateRouteArgs& a, hipStream_t stream) {
+  if (a.n_expert < 1 || a.n_expert > 64 || a.m < 1) return hipErrorInvalidValue;
+  switch (a.gate_t) {
+    case kActF32: return launch_gate_route_as<float>(a, stream);
+    case kActF16: return launch_gate_route_as<_Float16>(a, stream);
+    case kActBF16: return launch_gate_route_as<GateBf16>(a, stream);
+    default: return hipErrorInvalidValue;
+  }
 }
 
 // ------------------------------------------------------------------------------------------------ grouped: the sort
